@@ -244,6 +244,44 @@ def extra_record(argv, timeout_s):
         return {"error": f"{type(e).__name__}: {e}"[:300], "argv": argv, "wall_s": round(time.perf_counter() - t0, 1)}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_PER_TENSOR = 4096
+
+
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: each array as ``out_dir/<name>.npy`` (float64 for integer results, which it holds exactly; float32 otherwise)."""
+    import re
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.double() if not (t.is_floating_point() or t.is_complex()) else t.float()
+        host[re.sub(r"[^A-Za-z0-9_.-]", "_", name)] = t.cpu().numpy()
+    total = sum(v.nbytes for v in host.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes > {DUMP_LIMIT_BYTES}"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
+def train_outputs(model, loss, mod_loss, norm):
+    """What a caller of the timed train step holds after it: the loss, the per-modality losses, the gradient norm, and the updated
+    parameters - as a fixed sample (every tensor of up to DUMP_SAMPLE_PER_TENSOR elements whole, larger ones at that many seeded
+    positions), concatenated in named_parameters() order."""
+    out = {"loss": loss.reshape(1), "grad_norm": norm.reshape(1)}
+    out.update({f"mod_loss.{k}": v.reshape(1) for k, v in sorted(mod_loss.items())})
+    g = torch.Generator().manual_seed(0)
+    sample = []
+    for _, p in model.named_parameters():
+        flat = p.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE_PER_TENSOR:
+            idx = torch.randint(flat.numel(), (DUMP_SAMPLE_PER_TENSOR,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        sample.append(flat.float())
+    out["params_sample"] = torch.cat(sample)
+    return out
+
+
 def _cpu_model_name():
     try:
         return [l.split(":")[1].strip() for l in open("/proc/cpuinfo") if l.startswith("model name")][0]
@@ -475,6 +513,8 @@ def main_vq(a):
     fence()
     dt = time.perf_counter() - t0
     tok = toks[-1]
+    if a.dump_outputs and rank == 0:
+        write_outputs(a.dump_outputs, {"tokens": tok})
     t = torch.tensor([dt, dt1], device=dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -566,7 +606,7 @@ def main_divae(a):
         return
     from fourm.vq import decode_token_batches
     n_streams = a.vq_streams
-    steps, warmup = min(a.steps, 7), min(a.warmup, 1)
+    steps, warmup = a.steps, a.warmup
     for i in range(warmup):
         decode(i)
     decode_token_batches(model, [toks[i % 2] for i in range(n_streams + 1)], n_streams, timesteps=ddim, generator=gen, verbose=False)     # (per-stream scratch)
@@ -581,6 +621,8 @@ def main_divae(a):
     fence()
     dt = time.perf_counter() - t0
     img = imgs[-1]
+    if a.dump_outputs and rank == 0:
+        write_outputs(a.dump_outputs, {"images": img})
     t = torch.tensor([dt, dt1], device=dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -663,7 +705,11 @@ def main():
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-baseline-kind", default="auto", choices=["auto", "port", "reference"], help=argparse.SUPPRESS)
     ap.add_argument("--pmc-worker", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                    "(float32 / float64, at most 64 MB; the inputs are the same on every run with the same arguments)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     a.user_batch = a.batch
     # the sub-records of BASELINE configs[3] / [4] ride on the DEFAULT invocation only (N = 1, mod7, no size overrides)
     a.extras = not a.no_extras and a.workload == "train" and a.mods == "mod7" and a.batch is None and a.model is None and not a.pmc_worker and a.masking == "uniform" \
@@ -760,7 +806,7 @@ def main():
         norm = opt.fused_grad_norm(lazy=True)        # as the trainer without clipping (NativeScaler): the norm rides on the AdamW pass
         opt.step()
         opt.zero_grad(set_to_none=True)
-        return loss, norm
+        return loss, mod_loss, norm
 
     def fence():
         if world > 1:
@@ -773,13 +819,15 @@ def main():
         fence()
         return
     for i in range(a.warmup):
-        loss, norm = step(i)
+        step(i)
     fence()
     t0 = time.perf_counter()
     for i in range(a.steps):
-        loss, norm = step(i)
+        loss, mod_loss, norm = step(i)
     fence()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        write_outputs(a.dump_outputs, train_outputs(model, loss, mod_loss, norm))
     t = torch.tensor([dt], device=dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

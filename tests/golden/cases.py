@@ -96,3 +96,30 @@ VQVAE_CASES = {
                        channels=40, patch_proj=False),
     "vqvae_b224": dict(enc_type="vit_b_enc", dec_type="vit_b_dec", image=224, patch=16, codebook=16384, post_mlp=False, batch=2, seed=5, commitment_weight=0.25),
 }
+
+
+# ---- upstream pins (tests/golden/make_golden_upstream_pins.py): inputs and gradient sketches shared by the generator and the tests -------
+CODEBOOK_EMA_CASES = ((64, 500, 0.0), (256, 300, 0.25), (128, 40, 2.0))      # (codebook size K, rows, dead-code threshold)
+GRAD_PROJECTIONS = 16
+
+
+def codebook_ema_inputs(K: int, R: int):
+    """(codebook, cluster sizes, latents (2, R / 2, 32)) of one codebook-EMA case, from numpy's seeded generator (the same bits on
+    every machine): unit-norm rows, cluster sizes in [0, 3), latents N(0, 1.7^2)."""
+    import numpy as np
+    import torch
+    rng = np.random.default_rng([11, K, R])
+    e = rng.standard_normal((K, 32))
+    e /= np.linalg.norm(e, axis=1, keepdims=True)
+    c, z = rng.random(K) * 3, rng.standard_normal((2, R // 2, 32)) * 1.7
+    return tuple(torch.from_numpy(a.astype(np.float32)) for a in (e, c, z))
+
+
+def grad_projections(name: str, grad):
+    """Inner products (float64) of a gradient with GRAD_PROJECTIONS Gaussian directions seeded by the parameter's name: for an error E,
+    the mean square of its projections is an unbiased estimate of ||E||^2 that sees every entry."""
+    import zlib
+    import numpy as np
+    g = grad.detach().double().reshape(-1).numpy()
+    r = np.random.default_rng(zlib.crc32(name.encode())).standard_normal((GRAD_PROJECTIONS, g.size))
+    return r @ g

@@ -1,13 +1,13 @@
 """Host-side pieces of the generation API (no GPU): span-masking merge of generated sequences and the schedule dispatcher.
-The merge is pinned against upstream's own helpers when the reference tree is present (build container only)."""
-import importlib.util
+The merge is pinned against upstream's own helpers (their results on fixed inputs: tests/golden/upstream_pins.json)."""
+import json
 import os
 import random
 
 import pytest
 import torch
 
-REF = "/root/reference/fourm/utils/tokenizer/text_tokenizer.py"
+PINS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "upstream_pins.json")
 
 
 class FakeTokenizer:
@@ -37,19 +37,20 @@ def test_merge_span_masking_examples():
     assert s.merge_span_masking([5], [5, 30, 5, 31], sent) == [30, 31]                   # a repeated sentinel accumulates
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference tree not on this machine")
 def test_merge_matches_upstream_helpers():
-    spec = importlib.util.spec_from_file_location("ref_text_tokenizer", REF)
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
+    """upstream's get_sentinel_to_id_mapping / merge_span_masking (fourm/utils/tokenizer/text_tokenizer.py) on the same FakeTokenizer
+    and the same 200 random.Random(0) cases, recorded by tests/golden/make_golden_upstream_pins.py."""
+    pins = json.load(open(PINS))["merge_span"]
     s, tok = sampler(), FakeTokenizer()
     sent = s.sentinel_ids(tok)
-    assert sent == set(ref.get_sentinel_to_id_mapping(tok).values())
+    assert sent == set(pins["sentinel_ids"])
     rng = random.Random(0)
-    for _ in range(200):
+    for want_inp, want_dec, ref in pins["cases"]:
         inp = [rng.choice(list(range(5, 10)) + list(range(20, 40))) for _ in range(rng.randint(1, 12))]
         dec = [rng.choice(list(range(5, 10)) + list(range(20, 40))) for _ in range(rng.randint(0, 16))]
-        assert s.merge_span_masking(inp, dec, sent) == ref.merge_span_masking(inp, dec, sent)
+        assert (inp, dec) == (want_inp, want_dec)
+        assert s.merge_span_masking(inp, dec, sent) == ref
+    assert len(pins["cases"]) == 200
 
 
 def test_merge_sequences_batched_layout():

@@ -1,8 +1,8 @@
 """The trainer drop-in: ``ml-4m_amd/run_training_4m.py`` has upstream's command line and
 YAML surface; ``fourm.utils`` carries the schedules / loggers / run-name helpers the trainer calls; everything the package does not
-implement (``fourm.data`` loaders, vendored timm, ...) falls through to an upstream checkout.  Tests that need the upstream tree
-(``/root/reference``: present in the build container, absent on the GPU box) run in a child interpreter with this package FIRST on
-``sys.path`` and are skipped without it."""
+implement (``fourm.data`` loaders, vendored timm, ...) falls through to an upstream checkout.  What upstream's own get_args /
+schedules / setup_run_name return is recorded in tests/golden/upstream_pins.{json,npz} (tests/golden/make_golden_upstream_pins.py);
+the fall-through runs in a child interpreter with this package FIRST on ``sys.path`` against a stand-in checkout built in tmp_path."""
 import json
 import os
 import subprocess
@@ -14,58 +14,63 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "ml-4m_amd")
-REF = os.environ.get("FOURM_REFERENCE_ROOT", "/root/reference")
-needs_ref = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "fourm")), reason="no upstream checkout")
-YAML_B = os.path.join(REF, "cfgs/default/4m/models/main/4m-b_mod7_500b.yaml")
+PINS = os.path.join(ROOT, "tests", "golden", "upstream_pins")
 
 
-def child(code: str, upstream=True, timeout=600):
-    """Run ``code`` with [this package, repo root, upstream checkout] on sys.path (this package first: it shadows ``fourm``)."""
+def child(code: str, upstream=None, timeout=600):
+    """Run ``code`` with [this package, repo root] first on sys.path (this package shadows ``fourm``) and FOURM_UPSTREAM = ``upstream``."""
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
     env.pop("FOURM_UPSTREAM", None)
     if upstream:
-        env["FOURM_UPSTREAM"] = REF
+        env["FOURM_UPSTREAM"] = str(upstream)
     pre = f"import sys; sys.path[:0] = [{PKG!r}, {ROOT!r}]\n"
-    if upstream:       # inert torchvision / webdataset / ... stand-ins (install() also puts the upstream tree on sys.path: keep ours first)
-        pre += f"from tests.golden import ref_stubs; ref_stubs.install(); sys.path[:] = [{PKG!r}, {ROOT!r}] + [p for p in sys.path if p not in ({PKG!r}, {ROOT!r})]\n"
     r = subprocess.run([sys.executable, "-c", pre + textwrap.dedent(code)], capture_output=True, text=True, env=env, timeout=timeout, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     return r.stdout
 
 
-@needs_ref
-def test_upstream_get_args_runs_on_this_package_and_agrees_with_ours():
-    """Upstream's own ``get_args()`` (run_training_4m.py:42-239), imported with THIS package shadowing ``fourm`` (its module-level
-    ``from fourm.data import build_mixture_dataloader, ...`` and ``import fourm.utils as utils`` resolve through the fall-through),
-    parses upstream's 4M-B YAML; our ``get_args`` yields the identical namespace for the same command lines."""
-    out = child(f"""
-        import importlib.util, json, sys
-        spec = importlib.util.spec_from_file_location("upstream_trainer", {os.path.join(REF, 'run_training_4m.py')!r})
-        U = importlib.util.module_from_spec(spec); spec.loader.exec_module(U)
-        import run_training_4m as T
-        assert T.__file__.startswith({PKG!r}), T.__file__
-        import fourm; assert fourm.__file__.startswith({PKG!r})
-        cases = [["-c", {YAML_B!r}],
-                 ["-c", {YAML_B!r}, "--batch_size", "64", "--no_fixed_eval", "--opt_betas", "0.9", "0.99", "--clip_grad", "3.0", "--dtype", "bf16"],
-                 ["--epochs", "3", "--scheduler", "inverse_sqrt-10000", "--no_auto_resume", "--eval", "--log_wandb", "--find_unused_params"],
-                 ["-c", {os.path.join(REF, 'cfgs/default/4m/models/main/4m-l_mod21_500b.yaml')!r}, "--no_pin_mem", "--no_compute_grad_norm"]]
-        for argv in cases:
-            sys.argv = ["run_training_4m.py"] + argv
-            a, b = vars(U.get_args()), vars(T.get_args(argv))
-            assert a == b, sorted(set(a.items()) ^ set(b.items()), key=str)
-        a = U.get_args.__globals__["utils"]
-        print(json.dumps(dict(n=len(b), model=b["model"], utils_file=a.__file__)))
-    """)
-    info = json.loads(out.strip().splitlines()[-1])
-    assert info["n"] > 70 and info["utils_file"].startswith(PKG)
+def test_upstream_get_args_runs_on_this_package_and_agrees_with_ours(tmp_path):
+    """Upstream's own ``get_args()`` (run_training_4m.py:42-239) on upstream's 4M-B / 4M-L YAMLs and these command lines (its namespaces and
+    the YAMLs' contents recorded in the fixture): our ``get_args`` yields the identical namespace for the same command lines."""
+    import yaml
+    import run_training_4m as T
+    assert T.__file__.startswith(PKG), T.__file__
+    pins = json.load(open(PINS + ".json"))
+    paths = []
+    for name, data in pins["configs"]:
+        paths.append(str(tmp_path / name))
+        with open(paths[-1], "w") as f:
+            yaml.safe_dump(data, f)
+    for argv, want in pins["get_args"]:
+        want = {k: (paths[int(v[1:-1])] if isinstance(v, str) and v in ("{0}", "{1}") else v) for k, v in want.items()}
+        got = json.loads(json.dumps(vars(T.get_args([x.format(*paths) for x in argv]))))
+        assert got == want, sorted(set(map(str, got.items())) ^ set(map(str, want.items())))
+    assert len(want) > 70
 
 
-@needs_ref
-def test_fall_through_resolves_upstream_only_names():
+STAND_IN = {      # a stand-in upstream checkout: upstream-only names, plus names this package implements (ours must win)
+    "fourm/__init__.py": "",
+    "fourm/models/__init__.py": "",
+    "fourm/models/fm.py": "class FM:\n    pass\n",
+    "fourm/data/__init__.py": "".join(f"def {n}(*a, **k):\n    return '{n}'\n" for n in ("build_mixture_dataloader", "get_train_dataloader",
+                                                                                     "get_val_dataloader", "setup_sampling_mod_info")),
+    "fourm/data/masking.py": "class UnifiedMasking:\n    pass\n\n\ndef image_mask_batched(*a, **k):\n    pass\n",
+    "fourm/utils/__init__.py": "class ModelEma:\n    pass\n\n\nclass MetricLogger:\n    pass\n\n\ndef cosine_scheduler():\n    pass\n\n\n"
+                               "def create_model():\n    pass\n",
+    "fourm/utils/timm/__init__.py": "",
+    "fourm/utils/timm/model_ema.py": "class ModelEmaV2:\n    pass\n",
+    "run_training_4m.py": "import fourm.utils as utils\nfrom fourm.data import build_mixture_dataloader\n",
+}
+
+
+def test_fall_through_resolves_upstream_only_names(tmp_path):
+    for rel, src in STAND_IN.items():
+        (tmp_path / rel).parent.mkdir(parents=True, exist_ok=True)
+        (tmp_path / rel).write_text(src)
     out = child(f"""
         import fourm, fourm.utils as U, fourm.data as D
         from fourm.data import build_mixture_dataloader, get_train_dataloader, get_val_dataloader, setup_sampling_mod_info
-        ref = {REF!r}
+        ref = {str(tmp_path)!r}
         import inspect
         assert inspect.getsourcefile(build_mixture_dataloader).startswith(ref)          # upstream's function ...
         assert build_mixture_dataloader.__module__.startswith("fourm.data")             # ... living inside THIS package's namespace
@@ -79,8 +84,12 @@ def test_fall_through_resolves_upstream_only_names():
         assert inspect.getsourcefile(ModelEma).startswith(ref)
         from fourm.models.fm import FM
         assert inspect.getsourcefile(FM).startswith({PKG!r})
+        import importlib.util                                                             # upstream's trainer module sees THIS package
+        spec = importlib.util.spec_from_file_location("upstream_trainer", ref + "/run_training_4m.py")
+        M = importlib.util.module_from_spec(spec); spec.loader.exec_module(M)
+        assert M.utils.__file__.startswith({PKG!r}) and inspect.getsourcefile(M.build_mixture_dataloader).startswith(ref)
         print("ok")
-    """)
+    """, upstream=tmp_path)
     assert out.strip().endswith("ok")
 
 
@@ -96,45 +105,36 @@ def test_without_a_checkout_upstream_only_names_fail_loudly():
             else:
                 raise SystemExit(f"{name} resolved without an upstream checkout")
         print("ok")
-    """, upstream=False)
+    """)
     assert out.strip().endswith("ok")
 
 
-def _load_upstream(rel, name):
-    import importlib.util
-    spec = importlib.util.spec_from_file_location(name, os.path.join(REF, rel))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
-
-
-@needs_ref
 def test_schedules_equal_upstream():
     from fourm.utils import scheduler as S
-    U = _load_upstream("fourm/utils/scheduler.py", "upstream_scheduler")
-    for kw in (dict(base_value=1e-3, final_value=1e-6, epochs=5, niter_per_ep=37, warmup_epochs=1),
-               dict(base_value=2e-4, final_value=0.0, epochs=3, niter_per_ep=50, warmup_epochs=-1, warmup_steps=40),
-               dict(base_value=0.05, final_value=0.05, epochs=4, niter_per_ep=11)):
-        np.testing.assert_allclose(S.cosine_scheduler(**kw), U.cosine_scheduler(**kw), rtol=1e-12, atol=0)
-    for kw in (dict(base_value=1e-3, final_value=1e-5, epochs=6, niter_per_ep=40, warmup_epochs=1, cooldown_epochs=1, timescale=100),
-               dict(base_value=1e-3, final_value=1e-3, epochs=2, niter_per_ep=40, warmup_steps=7, cooldown_steps=9),
-               dict(base_value=4e-4, final_value=0.0, epochs=3, niter_per_ep=25)):
-        np.testing.assert_allclose(S.inverse_sqrt_scheduler(**kw), U.inverse_sqrt_scheduler(**kw), rtol=1e-12, atol=0)
-    np.testing.assert_array_equal(S.constant_scheduler(0.3, 2, 5), U.constant_scheduler(0.3, 2, 5))
+    U = np.load(PINS + ".npz")
+    for i, kw in enumerate((dict(base_value=1e-3, final_value=1e-6, epochs=5, niter_per_ep=37, warmup_epochs=1),
+                            dict(base_value=2e-4, final_value=0.0, epochs=3, niter_per_ep=50, warmup_epochs=-1, warmup_steps=40),
+                            dict(base_value=0.05, final_value=0.05, epochs=4, niter_per_ep=11))):
+        np.testing.assert_allclose(S.cosine_scheduler(**kw), U[f"schedule.cosine.{i}"], rtol=1e-12, atol=0)
+    for i, kw in enumerate((dict(base_value=1e-3, final_value=1e-5, epochs=6, niter_per_ep=40, warmup_epochs=1, cooldown_epochs=1, timescale=100),
+                            dict(base_value=1e-3, final_value=1e-3, epochs=2, niter_per_ep=40, warmup_steps=7, cooldown_steps=9),
+                            dict(base_value=4e-4, final_value=0.0, epochs=3, niter_per_ep=25))):
+        np.testing.assert_allclose(S.inverse_sqrt_scheduler(**kw), U[f"schedule.inverse_sqrt.{i}"], rtol=1e-12, atol=0)
+    np.testing.assert_array_equal(S.constant_scheduler(0.3, 2, 5), U["schedule.constant"])
 
 
-@needs_ref
 def test_run_name_equals_upstream():
     from argparse import Namespace
     from fourm.utils.run_name import setup_run_name
-    U = _load_upstream("fourm/utils/run_name.py", "upstream_run_name")
-    for kw in (dict(run_name="auto", config_path="cfgs/default/4m/models/main/4m-b_mod7_500b.yaml", wandb_run_name="auto",
-                    output_dir="output/auto", s3_save_dir="s3://bucket/auto/x"),
-               dict(run_name="mine", config_path="", wandb_run_name="auto", output_dir="out/auto"),
-               dict(run_name="auto", config_path="/abs/cfgs/a/b/c.yaml", output_dir="")):
-        a, b = Namespace(**kw), Namespace(**kw)
-        setup_run_name(a); U.setup_run_name(b)
-        assert vars(a) == vars(b)
+    pins = json.load(open(PINS + ".json"))["run_name"]
+    assert [kw for kw, _ in pins] == [dict(run_name="auto", config_path="cfgs/default/4m/models/main/4m-b_mod7_500b.yaml", wandb_run_name="auto",
+                                           output_dir="output/auto", s3_save_dir="s3://bucket/auto/x"),
+                                      dict(run_name="mine", config_path="", wandb_run_name="auto", output_dir="out/auto"),
+                                      dict(run_name="auto", config_path="/abs/cfgs/a/b/c.yaml", output_dir="")]
+    for kw, want in pins:
+        a = Namespace(**kw)
+        setup_run_name(a)
+        assert vars(a) == want
 
 
 def test_metric_logger_and_smoothed_value(capsys):
@@ -190,5 +190,5 @@ def test_synthetic_data_config_variants():
             assert ds["type"] == "synthetic" and ds["masking"] == want
             assert "rgb@224" in ds["in_domains"].split("-") and "rgb@224" not in ds["out_domains"].split("-")
         print("ok")
-    ''', upstream=False)
+    ''')
     assert "ok" in out
