@@ -397,7 +397,10 @@ int fm_maskgit_commit(const void* prob, const void* samples, const int32_t* mod_
 /* out[m][n] (+)= sum_k X[m*sxm + k*sxk] * W[n*swn + k*swk]  + epilogue (fm_epilogue without the *_BWD forms; no rounding).
  * Fully strided operands: NT (sxk = swk = 1), dX = dY W (swn = 1, swk = ldw) and dW = dY^T X (sxm = swn = 1, accumulate = 1)
  * are one kernel.  Grouped NT: groups + tile_group + seg_rows as in fm_gemm_nt (groups[g].W f32).  Grouped TN: groups[g].out /
- * .N with seg_start / seg_count (device), max_N = largest group N, n_groups; reduces rows [seg_start[g], + seg_count[g]). */
+ * .N with seg_start / seg_count (device), max_N = largest group N, n_groups; reduces rows [seg_start[g], + seg_count[g]).
+ * accumulate = 1 (out += result) only with FM_EPI_F32 / FM_EPI_BF16; GELU / TANH / RESIDUAL / SWIGLU with accumulate are refused
+ * (-1, fm_last_error).  Kernel choice: NT operands (sxk = swk = 1, no groups, not SWIGLU) with sxm % 4 == swn % 4 == 0 and 16-byte aligned X / W
+ * run on the fp32 matrix cores, everything else on an LDS-tiled FMA kernel; both give the same results within fp32 rounding. */
 typedef struct fm_gemm_f32_args {
     const void* X; const void* W; const void* W2; void* out; void* out2; const void* res; const void* bias; const void* bias2;
     int64_t sxm, sxk, swn, swk;

@@ -371,6 +371,10 @@ extern "C" int fm_gemm_f32(const fm_gemm_f32_args* p, void* stream) {
     FM_CHECK_ARG(p && p->X && (p->W || p->groups) && (p->out || p->seg_start), "fm_gemm_f32: null pointer");
     FM_CHECK_ARG(p->M > 0 || p->seg_start, "fm_gemm_f32: bad shape");
     FM_CHECK_ARG(p->epilogue != FM_EPI_SWIGLU_BWD && p->epilogue != FM_EPI_GELU_BWD, "fm_gemm_f32: activation-backward epilogues are separate kernels here");
+    // accumulate adds the plain fp32 result to out; an activation or residual epilogue has no accumulating form (the two kernels
+    // below would disagree on it), so the combination is refused rather than given a meaning that depends on operand alignment
+    FM_CHECK_ARG(!p->accumulate || p->epilogue == FM_EPI_F32 || p->epilogue == FM_EPI_BF16,
+                 "fm_gemm_f32: accumulate is defined for the F32 / BF16 epilogues only (epilogue %d)", p->epilogue);
     const int maxN = p->groups && p->tile_group ? p->max_N : p->N;
     const int maxM = p->seg_start ? p->max_N : p->M;
     dim3 grid((maxN + 63) / 64, (maxM + 63) / 64, p->seg_start ? p->n_groups : 1);

@@ -6,9 +6,12 @@ import math
 import pytest
 import torch
 
+from tests.parity_log import record
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
+U32 = 2.0 ** -24         # fp32 unit roundoff
 
 
 def _ops():
@@ -535,6 +538,175 @@ def test_gemm_grouped():
             s = int(seg_start[h])
             ref = logits[s:s + len(rows), :vocabs[h]].float().t() @ y[rows].float() if len(rows) else torch.zeros_like(dws[h])
             assert rel_err(dws[h], ref) < 1e-4 or float(ref.norm()) == 0.0, (tr, h)
+
+
+CE_VOCABS = [30000, 16384, 8192, 4096, 23, 512]          # the real heads' vocabularies (oracle/fourm_oracle.py:606-633), a tiny one, an empty head
+CE_COUNTS = [301, 257, 70, 129, 33, 0]                   # rows per head: none a multiple of ops.SEG
+
+
+def segmented_ce_problem(dtype, seed=70):
+    """Decoder rows of len(CE_VOCABS) heads segmented by fm_segment_rows (as in test_gemm_grouped), with logits written directly into
+    the (Rp, ldl) segmented layout: N(0, 3) rows, confident rows (one logit at +60, target on it or at the row's minimum), rows shifted
+    to -40, one constant row (all ties) per head, targets 0 and V - 1 in every live head.  Columns [V, roundup64(V)) of live rows hold
+    3.0 (never read as logits), pad rows of live segments 5.0, everything else the sentinel 7.0.  Returns a dict of the device buffers
+    and the float64 logits of every head's rows (the values the kernel reads, after rounding to ``dtype``)."""
+    ops, L = _ops()
+    n_heads = len(CE_VOCABS)
+    R = sum(CE_COUNTS) + 45                               # 45 decoder rows belong to no head
+    head = torch.full((R,), -1, dtype=torch.int32)
+    idx = torch.randperm(R, generator=torch.Generator().manual_seed(seed))
+    o = 0
+    for h, c in enumerate(CE_COUNTS):
+        head[idx[o:o + c]] = h
+        o += c
+    head = head.to(DEV)
+    Rp = ops.padded_rows(R, n_heads)
+    seg_start = torch.zeros(n_heads, dtype=torch.int32, device=DEV)
+    seg_count = torch.zeros_like(seg_start)
+    perm = torch.zeros(Rp, dtype=torch.int32, device=DEV)
+    r2p = torch.zeros(R, dtype=torch.int32, device=DEV)
+    tile_group = torch.zeros(Rp // ops.SEG, dtype=torch.int32, device=DEV)
+    ops.segment_rows(head, n_heads, seg_start, seg_count, perm, r2p, tile_group)
+    assert seg_count.tolist() == CE_COUNTS
+    ldl = ops.ru(max(CE_VOCABS), 64) + 64                 # every head has sentinel columns past roundup64(V)
+    logits = torch.full((Rp, ldl), 7.0, device=DEV, dtype=dtype)
+    tgt = torch.zeros(R, dtype=torch.int64)
+    g = torch.Generator().manual_seed(seed + 1)
+    x64 = []
+    for h, (v, c) in enumerate(zip(CE_VOCABS, CE_COUNTS)):
+        s = int(seg_start[h])
+        logits[s:s + ops.ru(c, ops.SEG), :ops.ru(v, 64)] = 5.0
+        if c == 0:
+            x64.append(None)
+            continue
+        x = torch.randn(c, v, generator=g) * 3.0
+        t = torch.randint(0, v, (c,), generator=g)
+        for i in range(c):
+            kind = i % 6
+            if kind in (1, 2):                            # confident row: max |x| = 60
+                j = int(torch.randint(0, v, (1,), generator=g))
+                x[i, j] = 60.0
+                t[i] = j if kind == 1 else int(x[i].argmin())
+            elif kind == 3:
+                x[i] -= 40.0
+        x[0] = 1.5                                        # all ties
+        t[1], t[2 % c] = 0, v - 1                         # first and last column as targets
+        if c > 3:
+            x[3, v - 1] = 60.0                            # ... and a confident row whose arg-max is the last column
+            t[3] = v - 1
+        xd = x.to(dtype)
+        logits[s:s + c, :v] = xd.to(DEV)
+        logits[s:s + c, v:ops.ru(v, 64)] = 3.0
+        tgt[torch.nonzero(head.cpu() == h).flatten()] = t
+        x64.append(xd.double().to(DEV))
+    return dict(ops=ops, L=L, n_heads=n_heads, R=R, Rp=Rp, head=head, seg_start=seg_start, seg_count=seg_count, perm=perm, r2p=r2p,
+                tile_group=tile_group, logits=logits, ldl=ldl, tgt=tgt.to(DEV), vocab_t=torch.tensor(CE_VOCABS, dtype=torch.int32, device=DEV),
+                x64=x64)
+
+
+def ce_reference(pb, loss_type_name, grad_scale):
+    """float64 restatement of fm.py:573-637 on the logits the kernel reads: per-row lse / loss, per-head means (0 for an empty head),
+    the 'mod' / 'token' total and d(total * grad_scale)/d(logits) = coef_h * (softmax - onehot)."""
+    lse, loss, hl, grads, numel = [], [], [], [], []
+    for h, (v, c) in enumerate(zip(CE_VOCABS, CE_COUNTS)):
+        if c == 0:
+            lse.append(None); loss.append(None); grads.append(None); hl.append(0.0); numel.append(0)
+            continue
+        x = pb["x64"][h]
+        t = pb["tgt"][torch.nonzero(pb["head"] == h).flatten()]
+        l = torch.logsumexp(x, -1)
+        lse.append(l)
+        loss.append(l - x.gather(1, t[:, None]).squeeze(1))
+        hl.append(float(loss[-1].mean()))
+        numel.append(c * v)
+        oh = torch.zeros_like(x)
+        oh[torch.arange(c, device=DEV), t] = 1.0
+        grads.append((torch.exp(x - l[:, None]) - oh, t))
+    n = len(CE_VOCABS)
+    if loss_type_name == "mod":
+        total, coef = sum(hl) / n, [grad_scale / (n * c) if c else 0.0 for c in CE_COUNTS]
+    else:
+        total, coef = sum(a * b for a, b in zip(hl, numel)) / sum(numel), [grad_scale * v / sum(numel) for v in CE_VOCABS]
+    return dict(lse=lse, loss=loss, head_loss=hl, total=total, grads=grads, coef=coef, numel=numel)
+
+
+@pytest.mark.parametrize("loss_type", ["mod", "token"])
+def test_cross_entropy_production_vocabularies(loss_type):
+    """fm_cross_entropy (ce_fwd_kernel / loss_finalize_kernel / ce_bwd_kernel, the timed bf16 path) at the real heads' vocabularies
+    against a float64 logsumexp of the same bf16 logits: the online max / sum merge over 8-wide chunks, waves and workgroups, the
+    c + 8 <= V tail (30000 and 23 are not multiples of 8 * 256 or 64), targets in the first and last column, confident rows far from
+    zero, an all-ties row, an empty head, pad rows and pad columns, and columns the kernel must not touch."""
+    ops, L = _ops()
+    pb = segmented_ce_problem(torch.bfloat16)
+    logits, n_heads, Rp = pb["logits"], pb["n_heads"], pb["Rp"]
+    before = logits.clone()
+    gs = 0.5
+    ref = ce_reference(pb, loss_type, gs)
+    lt = L.LOSS_MOD if loss_type == "mod" else L.LOSS_TOKEN
+    row_loss, row_lse = torch.full((Rp,), 9.0, device=DEV), torch.full((Rp,), 9.0, device=DEV)
+    head_loss, total = torch.zeros(n_heads, device=DEV), torch.zeros(1, device=DEV)
+    args = (pb["perm"], pb["tile_group"], pb["tgt"], pb["vocab_t"], pb["seg_start"], pb["seg_count"], n_heads, max(CE_VOCABS))
+    ops.cross_entropy(logits, *args, row_loss, row_lse, head_loss, total, loss_type=lt)
+    assert torch.equal(logits, before)                                          # the forward only reads
+    # Bound of row_lse / row_loss, derived: __expf(t) = v_exp_f32(t log2 e) is off by <= (|t| + 1) u relative, and a term with t = x - m
+    # weighs e^-t, so exp errors add <= (1/e + 1) u of the sum per merge; a thread's sum takes <= 8 + 2 V / 2048 sequential roundings,
+    # then 6 shuffle and 3 wave merges of <= 5 u each, with V / 2048 online rescales of <= 2 u each: <= 140 u = 8.4e-6 relative at
+    # V = 30000, the same absolute error on lse.  __logf adds 2 ulp of log S (< 2e-6) and m + log S rounds by u |lse|, so
+    # |row_lse - lse| <= 1e-5 * max(1, |lse|).  row_loss = lse - x[target] rounds once more (u |loss|).
+    worst = dict(lse=0.0, loss=0.0, grad=0.0)
+    for h, (v, c) in enumerate(zip(CE_VOCABS, CE_COUNTS)):
+        s = int(pb["seg_start"][h])
+        padr = slice(s + c, s + ops.ru(c, ops.SEG))
+        assert float(row_loss[padr].abs().max() if c % ops.SEG else 0.0) == 0.0 and float(row_lse[padr].abs().max() if c % ops.SEG else 0.0) == 0.0
+        if c == 0:
+            assert float(head_loss[h]) == 0.0
+            continue
+        pr = pb["r2p"][torch.nonzero(pb["head"] == h).flatten()].long()
+        assert torch.equal(pr, torch.arange(s, s + c, device=DEV))
+        lse_ref, loss_ref = ref["lse"][h], ref["loss"][h]
+        bound = 1e-5 * lse_ref.abs().clamp(min=1.0)
+        e_lse = (row_lse[s:s + c].double() - lse_ref).abs()
+        e_loss = (row_loss[s:s + c].double() - loss_ref).abs()
+        assert bool((e_lse <= bound).all()), (v, float((e_lse / bound).max()))
+        assert bool((e_loss <= bound + U32 * loss_ref.abs()).all()), (v, float((e_loss / bound).max()))
+        worst["lse"] = max(worst["lse"], float((e_lse / lse_ref.abs().clamp(min=1.0)).max()))
+        worst["loss"] = max(worst["loss"], float((e_loss / lse_ref.abs().clamp(min=1.0)).max()))
+        # head mean: the row bounds averaged, plus the 256-thread tree sum of c non-negative terms ((c / 256 + 10) u of the sum)
+        hb = float(bound.mean()) + (c / 256 + 10) * U32 * ref["head_loss"][h]
+        assert abs(float(head_loss[h]) - ref["head_loss"][h]) <= hb, (v, float(head_loss[h]), ref["head_loss"][h])
+    hbs = [1e-5 * float(l.abs().clamp(min=1.0).mean()) + (c / 256 + 10) * U32 * hl if l is not None else 0.0
+           for l, c, hl in zip(ref["lse"], CE_COUNTS, ref["head_loss"])]
+    w = [1.0] * n_heads if loss_type == "mod" else ref["numel"]
+    tb = sum(a * b for a, b in zip(hbs, w)) / sum(w) + 4 * (n_heads + 2) * U32 * abs(ref["total"])
+    assert abs(float(total) - ref["total"]) <= tb, (float(total), ref["total"])
+    # backward in place
+    ops.cross_entropy(logits, *args, row_loss, row_lse, head_loss, total, loss_type=lt, grad_scale=torch.tensor([gs], device=DEV), write_grad=True)
+    covered = torch.zeros(Rp, pb["ldl"], dtype=torch.bool, device=DEV)
+    for h, (v, c) in enumerate(zip(CE_VOCABS, CE_COUNTS)):
+        s, vp = int(pb["seg_start"][h]), ops.ru(v, 64)
+        covered[s:s + ops.ru(c, ops.SEG), :vp] = True
+        if c == 0:
+            continue
+        got = logits[s:s + c, :v].double()
+        p_oh, t = ref["grads"][h]
+        want = ref["coef"][h] * p_oh
+        # the kernel's value before the bf16 store: __expf(x - lse) with lse off by <= 1e-5 max(1, |lse|) and (x - lse) scaled by
+        # log2 e (2 (|x - lse| + 2) u relative), minus the one-hot (u), times the fp32 coefficient (3 u): E; then bf16 round to
+        # nearest: |got - want| <= 2^-8 |want| + (1 + 2^-8) E.  E includes the underflow term (|coef| + 1) 2^-126: probabilities below
+        # the fp32 normal range (e^-100 in the confident rows) are flushed to zero
+        x, lse = pb["x64"][h], ref["lse"][h][:, None]
+        p = torch.exp(x - lse)
+        E = abs(ref["coef"][h]) * (p * (1e-5 * lse.abs().clamp(min=1.0) + 2 * U32 * ((x - lse).abs() + 2)) + 4 * U32 * p_oh.abs())
+        E = E + (abs(ref["coef"][h]) + 1) * 2.0 ** -126
+        err = (got - want).abs()
+        tol = 2 ** -8 * want.abs() + 2 * E
+        assert bool((err <= tol).all()), (v, float((err / tol).max()))
+        worst["grad"] = max(worst["grad"], float((err / (want.abs() + E)).max()))
+        assert float(logits[s + c:s + ops.ru(c, ops.SEG), :vp].float().abs().max() if c % ops.SEG else 0.0) == 0.0      # pad rows
+        assert float(logits[s:s + c, v:vp].float().abs().max() if vp > v else 0.0) == 0.0                               # pad columns
+    assert bool((logits[~covered] == 7.0).all())                                                                         # untouched
+    record(f"kernels.cross_entropy_bf16.{loss_type}", lse_abs_rel_worst=worst["lse"], loss_abs_rel_worst=worst["loss"],
+           grad_rel_worst=worst["grad"], total_err=abs(float(total) - ref["total"]))
 
 
 # ------------------------------------------------------------------------------------------------

@@ -142,7 +142,7 @@ def test_logits(name):
     assert worst_f32 < b_f32, errs
 
 
-@pytest.mark.parametrize("name", ["micro_swiglu", "micro_pad", "micro_gelu", "micro_qknorm", "ti_mod7", "l_like", "b_mod7"])
+@pytest.mark.parametrize("name", ["micro_swiglu", "micro_pad", "micro_gelu", "micro_qknorm", "ti_mod7", "l_like", "b_mod7", "l_mod21"])
 def test_fp32_verification_mode(name):
     """compute_precision = "fp32": the SAME engine (selection, launch sequence, hand-written backward, segmented heads) on the
     fp32 verification kernels (csrc/fp32_verify.hip), no bf16 rounding anywhere, against the upstream fp32 model (the oracle in
