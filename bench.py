@@ -10,6 +10,12 @@ synthetic random-token multimodal batches, per-GPU batch 256, 128 input + 128 ta
 A step = select+embed -> encoder -> decoder -> heads/CE -> hand-written backward -> (RCCL gradient
 mean, overlapped with backward) -> gradient norm -> fused AdamW.  Inputs are resident in HBM before
 the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: nothing else.
+--full adds what takes time of its own: the per-kernel breakdown and roofline (two extra steps, plus
+rocprofv3 PMC passes for the traffic), the CPU baseline, the parity record, the one-at-a-time figures of
+--workload vq / divae, the producer time of --masking dirichlet and, on the default invocation, the
+extra.vq / extra.mod21 / extra.divae sub-records.  The --no-* options switch parts of --full off.
 """
 import argparse
 import json
@@ -236,7 +242,7 @@ def extra_record(argv, timeout_s):
             base, ext = os.path.splitext(env["BENCH_SHAPE_TABLE"])
             tag = "_".join(x.lstrip("-") for x in argv[:2])
             env["BENCH_SHAPE_TABLE"] = f"{base}_{tag}{ext}"
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--no-extras", *argv], capture_output=True, text=True, timeout=timeout_s, env=env)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--no-extras", *argv], capture_output=True, text=True, timeout=timeout_s, env=env)
         rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
         rec["wall_s"] = round(time.perf_counter() - t0, 1)
         return rec
@@ -501,12 +507,13 @@ def main_vq(a):
         model.tokenize(xs[i % 2])
     tokenize_sub_batches(model, [xs[i % 2] for i in range(2 * n_streams + 1)], n_streams)       # (allocates the per-stream scratch sets)
     fence()
-    # one sub-batch at a time (the number of rounds 1 - 5) ...
-    t0 = time.perf_counter()
-    for i in range(a.steps):
-        tok = model.tokenize(xs[i % 2])
-    fence()
-    dt1 = time.perf_counter() - t0
+    dt1 = None
+    if a.full:      # one sub-batch at a time (the number of rounds 1 - 5) ...
+        t0 = time.perf_counter()
+        for i in range(a.steps):
+            tok = model.tokenize(xs[i % 2])
+        fence()
+        dt1 = time.perf_counter() - t0
     # ... and the timed region: upstream's loop over sub-batches of 64 (save_vq_tokens.py:262-288) with two of them in flight on two HIP streams
     t0 = time.perf_counter()
     toks = tokenize_sub_batches(model, [xs[i % 2] for i in range(a.steps)], n_streams)
@@ -515,7 +522,7 @@ def main_vq(a):
     tok = toks[-1]
     if a.dump_outputs and rank == 0:
         write_outputs(a.dump_outputs, {"tokens": tok})
-    t = torch.tensor([dt, dt1], device=dev)
+    t = torch.tensor([dt, dt1 or 0.0], device=dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt, dt1 = float(t[0]), float(t[1])
@@ -527,9 +534,10 @@ def main_vq(a):
            "config": {"workload": "RGB VQ tokenizer (ViT-B/16 encoder 90.5M params, 224^2 -> 14x14 codes, 16384 x 32 cosine codebook): "
                                   "VQ.tokenize on uniform [-1,1] images", "per_gpu_batch": batch, "global_batch": batch * world,
                       "parallelism": f"replicas x{world}; {n_streams} sub-batches of {batch} in flight on {n_streams} HIP streams (fourm.vq.tokenize_sub_batches)"},
-           "one_sub_batch_in_flight_images_per_s": world * batch * a.steps / dt1,
            "codes_per_sec": value * 196, "mfu": flops_img * value / world / (BF16_PEAK_TFLOPS * 1e12),
            "arithmetic": "ViT blocks bf16 operands / fp32 accumulate; post-MLP, 1x1 projection and code search fp32"}
+    if a.full:
+        out["one_sub_batch_in_flight_images_per_s"] = world * batch * a.steps / dt1
     if not a.no_kernel_profile and rank == 0:
         prof = LaunchProfiler()
         ops.set_profiler(prof)
@@ -611,7 +619,8 @@ def main_divae(a):
         decode(i)
     decode_token_batches(model, [toks[i % 2] for i in range(n_streams + 1)], n_streams, timesteps=ddim, generator=gen, verbose=False)     # (per-stream scratch)
     fence()
-    t0 = time.perf_counter()                   # one decode at a time ...
+    # one decode at a time ... (also without --full: the timed decodes draw their start noise from `gen` where these two leave it)
+    t0 = time.perf_counter()
     for i in range(2):
         img = decode(i)
     fence()
@@ -635,10 +644,11 @@ def main_divae(a):
            "config": {"workload": "DiVAE detokenizer (unet_patched decoder 196 M parameters, 56 x 56 patch grid, 14 x 14 x 32 conditioning, DDIM 25 steps, "
                                   "dynamic thresholding): DiVAE.decode_tokens on random token grids", "per_gpu_batch": batch, "global_batch": batch * world,
                       "parallelism": f"replicas x{world}; {n_streams} decodes of batch {batch} in flight on {n_streams} HIP streams (fourm.vq.decode_token_batches)"},
-           "ms_per_unet_evaluation_one_decode_in_flight": 1e3 * dt1 / ddim, "one_decode_in_flight_images_per_s": world * batch / dt1,
-           "finite": bool(torch.isfinite(img).all()),
            "mfu": flops_img_eval * ddim * value / world / (BF16_PEAK_TFLOPS * 1e12),
            "arithmetic": "convolutions as im2col + bf16 GEMMs (fp32 accumulate), bf16 feature maps, GroupNorm / attention softmax / scheduler steps fp32"}
+    if a.full:
+        out.update({"ms_per_unet_evaluation_one_decode_in_flight": 1e3 * dt1 / ddim, "one_decode_in_flight_images_per_s": world * batch / dt1,
+                    "finite": bool(torch.isfinite(img).all())})
     if not a.no_kernel_profile and rank == 0:
         prof = LaunchProfiler()
         quant = model.tokens_to_embedding(toks[0]).float()
@@ -695,13 +705,16 @@ def main():
     ap.add_argument("--n-out", type=int, default=None)
     ap.add_argument("--masking", default="uniform", choices=["uniform", "dirichlet"], help="uniform = SURVEY §8d's synthetic budgets (the headline); "
                     "dirichlet = the batches come from the device-side masking pipeline (Dirichlet token budgets, image masks, span masking: "
-                    "fourm.data.masking.DeviceUnifiedMasking), and the record carries the producer's time per batch")
+                    "fourm.data.masking.DeviceUnifiedMasking); with --full the record carries the producer's time per batch")
     ap.add_argument("--vq-streams", type=int, default=2, help="--workload vq: sub-batches of 64 in flight (HIP streams) in the timed region")
+    ap.add_argument("--full", action="store_true", help="besides the headline figure: per-kernel breakdown + roofline (+ rocprofv3 PMC traffic), CPU baseline, "
+                    "parity record, the one-at-a-time figures of --workload vq / divae, the producer time of --masking dirichlet, and on the default "
+                    "invocation the extra.vq / extra.mod21 / extra.divae sub-records (the --no-* options below switch parts of it off)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-profile", action="store_true")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, default) | gloo (test hook: several ranks on one GPU)")
     ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 --pmc passes that fill roofline.traffic")
-    ap.add_argument("--no-extras", action="store_true", help="headline record only (default for non-default workloads): no extra.vq / extra.mod21 sub-records")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no extra.vq / extra.mod21 / extra.divae sub-records (only the default invocation has them)")
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-baseline-kind", default="auto", choices=["auto", "port", "reference"], help=argparse.SUPPRESS)
     ap.add_argument("--pmc-worker", action="store_true", help=argparse.SUPPRESS)
@@ -711,6 +724,8 @@ def main():
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
     a.user_batch = a.batch
+    if not a.full:      # a plain run: the headline figure only
+        a.no_cpu_baseline = a.no_kernel_profile = a.no_traffic = a.no_extras = True
     # the sub-records of BASELINE configs[3] / [4] ride on the DEFAULT invocation only (N = 1, mod7, no size overrides)
     a.extras = not a.no_extras and a.workload == "train" and a.mods == "mod7" and a.batch is None and a.model is None and not a.pmc_worker and a.masking == "uniform" \
         and not a.cpu_baseline_worker and a.gpus == 1 and a.dist_backend == "nccl" and not a.no_cpu_baseline
@@ -790,11 +805,12 @@ def main():
         gen = torch.Generator(device=dev).manual_seed(1000 * rank)
         batches = [device_masked_batch(model, um, a.batch, device=dev, generator=gen) for _ in range(2)]
         torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(5):
-            device_masked_batch(model, um, a.batch, device=dev, generator=gen)
-        torch.cuda.synchronize()
-        masking_ms = (time.perf_counter() - t0) / 5 * 1e3
+        if a.full:
+            t0 = time.perf_counter()
+            for _ in range(5):
+                device_masked_batch(model, um, a.batch, device=dev, generator=gen)
+            torch.cuda.synchronize()
+            masking_ms = (time.perf_counter() - t0) / 5 * 1e3
     else:
         batches = [synthetic_batch(model, a.batch, a.n_in, a.n_out, device=dev, seed=1000 * rank + i) for i in range(2)]
     import random
@@ -863,8 +879,9 @@ def main():
                                           "NCCL_MAX_NCHANNELS": os.environ.get("NCCL_MAX_NCHANNELS"), **(comm_check or {}), **(exch or {}),
                                           "note": "exposed_ms_per_step = rank 0's compute stream between entering GradReducer.finish() and holding every "
                                                   "reduced slice (collectives still running or not yet started + unpack), averaged over the timed steps"}
-    if masking_ms is not None:
+    if a.masking == "dirichlet":
         out["data"] = "synthetic modalities masked on the device (Dirichlet token budgets, image masks, span masking)"
+    if masking_ms is not None:
         out["masking_ms_per_batch"] = masking_ms          # the producer, outside the timed region (batches are resident when it starts)
 
     # ---- dominant kernel vs its roofline, measured live with events on the launch stream (rank 0) ----------
@@ -920,7 +937,7 @@ def main():
                 f.write("\n".join(prof.shape_table(2)) + "\n")
     if world > 1:
         dist.barrier()
-    if rank == 0 and a.mods == "mod7":
+    if rank == 0 and a.mods == "mod7" and a.full:
         out["parity"] = parity_record()
     if rank == 0 and world == 1 and not a.no_cpu_baseline:
         print(json.dumps(out), file=sys.stderr)      # the GPU result is safe on stderr before the CPU leg starts
