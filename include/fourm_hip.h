@@ -480,8 +480,8 @@ int fm_tanh_bwd_f32(const void* dy, const void* t, void* dx, int R, int N, int l
 int fm_embed_rows_f32(const void* table, const int64_t* idx, void* out, int ld_out, int R, int D, void* stream);
 /* fp32 products on the bf16 matrix cores: out (R, ldo >= 3 K) bf16 = [hi | hi | lo] of x f32 (R, K) (weight_order = 0: the activation
  * operand) or [hi | lo | hi] (weight_order = 1: the weight operand), hi = bf16(x), lo = bf16(x - hi); apply_tanh: x <- tanh(x) first.
- * ONE bf16 NT GEMM over the 3 K columns then accumulates hi hi + hi lo + lo hi in fp32: ~2^-16 relative (the tokenizer's fp32 tail at
- * inference, vit_models.py:494-496). */
+ * ONE bf16 NT GEMM over the 3 K columns then accumulates hi hi + hi lo + lo hi in fp32: error within 3 * 2^-16 of sum |x| |w|, measured
+ * <= 2.2e-6 of it (the tokenizer's fp32 tail at inference, vit_models.py:494-496). */
 int fm_split3_bf16(const void* x, int ldx, void* out, int ldo, int R, int K, int weight_order, int apply_tanh, void* stream);
 /* Input variants of the tokenizer (VQ.prepare_input, vq/vqvae.py:269-286) folded into the patch gather: fm_vq_patchify with
  *   labels != NULL: class maps int64 (B, H, W) embedded by cls_emb f32 (n_labels, C) (semantic segmentation, n_labels; img unused);

@@ -179,3 +179,47 @@ def test_gradients_accumulate_and_frozen_encoder():
     assert torch.allclose(f.decoder.out_proj.weight.grad, g1["decoder.out_proj.weight"], rtol=1e-3, atol=1e-6)
     with torch.no_grad():
         assert not f(xg)[0].requires_grad
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("optim", ["fused", "torch"])
+def test_eval_encode_after_optimizer_step_uses_new_weights(optim):
+    """The inference tail caches the [hi | lo | hi] bf16 images of post_mlp.fc1 / fc2 (vq/engine.py _split3_weight).  FusedAdamW writes
+    parameters through raw pointers (no _version bump) and signals it with bump_weight_epoch(): after one training step an eval-mode
+    encode must see the new weights, i.e. match a fresh model loaded from the trained state_dict (torch.optim.AdamW: the control)."""
+    from fourm.utils.optim_factory import FusedAdamW
+
+    def make():
+        from fourm.vq import VQVAE
+        return VQVAE(dec_type="vit_s_dec", image_size=32, enc_type="vit_s_enc", patch_size=8, post_mlp=True, codebook_size=64, latent_dim=32,
+                     norm_codes=True, sync_codebook=False, threshold_ema_dead_code=0)
+
+    torch.manual_seed(0)
+    m = make().cuda()
+    assert m.encoder.post_mlp.fc1.weight.shape == (2048, 512)               # D % 64 == 0 and hid % 64 == 0: the split3 tail runs
+    x = torch.randn(2, 3, 32, 32, generator=torch.Generator().manual_seed(1)).cuda()
+    m.eval()
+    m.encode(x)                                                             # fills the split3 weight cache
+    lat0 = m._last_latents.clone()
+    m.train()
+    params = [p for p in m.parameters() if p.requires_grad]
+    opt = FusedAdamW(params, lr=1e-2) if optim == "fused" else torch.optim.AdamW(params, lr=1e-2)
+    dec, cl = m(x)
+    (F.mse_loss(dec, x) + cl.sum()).backward()
+    w_before = m.encoder.post_mlp.fc1.weight.detach().clone()
+    opt.step()
+    assert not torch.equal(m.encoder.post_mlp.fc1.weight.detach(), w_before)
+    m.eval()
+    tok1 = m.encode(x)[2]
+    lat1 = m._last_latents.clone()
+    dec1 = m.decode_tokens(tok1)
+    f = make()
+    f.load_state_dict(m.state_dict(), strict=True)
+    f = f.cuda().eval()
+    tokf = f.encode(x)[2]
+    latf = f._last_latents.clone()
+    decf = f.decode_tokens(tokf)
+    assert _rel(lat1, lat0) > 1e-3                                           # the step moved the latents
+    assert _rel(lat1, latf) <= 1e-6, (optim, _rel(lat1, latf))
+    assert torch.equal(tok1, tokf), optim
+    assert _rel(dec1, decf) <= 1e-6, (optim, _rel(dec1, decf))
