@@ -21,7 +21,10 @@ namespace {
 // ------------------------------------------------------------------------------------------------------------------------------------
 // im2col: out[(b, oy, ox)][tap * C + c] = in[b][oy * stride + ky - pad][ox * stride + kx - pad][c]   (zero outside), C = C1 + C2
 //   in = [src1 | src2] along channels; src1 is read at (y >> up1, x >> up1) (nearest x2 up-sampling when up1 = 1), src2 at
-//   (y * H2 / H, x * W2 / W) (nearest: the skip tensor at the same resolution, or the 14 x 14 conditioning under the 56 x 56 grid).
+//   (min(floorf(y * sy), H2 - 1), min(floorf(x * sx), W2 - 1)) with sy = fp32(H2) / fp32(H), sx = fp32(W2) / fp32(W) divided on the host:
+//   the index rule of F.interpolate(mode="nearest") on fp32 maps (unet.py:732), bit for bit, for every pair of grids (the skip tensor at
+//   the same resolution, the 14 x 14 conditioning under the 56 x 56 grid).  The integer rule y * H2 / H that stood here differs from it
+//   by a row where fp32(H2 / H) rounds down, e.g. 14 under 46.
 // ------------------------------------------------------------------------------------------------------------------------------------
 struct Im2colArgs {
     const bf16_t* src1; const bf16_t* src2; bf16_t* out;
@@ -30,6 +33,7 @@ struct Im2colArgs {
     int C1, C2, H2, W2;
     int Ho, Wo, ksize, stride, up1;
     int kpad;               // columns [ksize^2 * C, kpad) are written as zeros (GEMM reduction padding)
+    float sy2, sx2;         // (float)H2 / (float)H, (float)W2 / (float)W
 };
 
 __global__ __launch_bounds__(256) void im2col_kernel(Im2colArgs a) {
@@ -51,7 +55,7 @@ __global__ __launch_bounds__(256) void im2col_kernel(Im2colArgs a) {
                     const int sy = y >> a.up1, sx = x >> a.up1, sw = a.W >> a.up1, sh = a.H >> a.up1;
                     val = *(const uint4*)(a.src1 + ((size_t)(b * sh + sy) * sw + sx) * a.ld1 + c);
                 } else {
-                    const int sy = y * a.H2 / a.H, sx = x * a.W2 / a.W;
+                    const int sy = min((int)floorf((float)y * a.sy2), a.H2 - 1), sx = min((int)floorf((float)x * a.sx2), a.W2 - 1);
                     val = *(const uint4*)(a.src2 + ((size_t)(b * a.H2 + sy) * a.W2 + sx) * a.ld2 + (c - a.C1));
                 }
             }
@@ -70,7 +74,9 @@ __global__ __launch_bounds__(256) void im2col_kernel(Im2colArgs a) {
 // and writes (sum, sum of squares) of its rows to partial[b][chunk][g]; gn_finalize_kernel adds the chunks in order.  B * HW / 32
 // workgroups stream the map once (the first form - one workgroup per (sample, group) gathering 2-byte values at a row stride - took as
 // long as the convolution GEMMs on the 56 x 56 maps).  Sums are taken about a per-group SHIFT (the group's first value of the sample):
-// E[d^2] - E[d]^2 then does not cancel for maps with a large mean.
+// E[d^2] - E[d]^2 then cancels only as far as that value lies from the group's mean - the variance carries an error of about
+// L u (var + (mean - shift)^2), L the length of the summation chain, so a map with a large mean costs nothing, while a group whose FIRST
+// value is an outlier of k standard deviations loses about k^2 L u of relative accuracy (tests/test_divae_kernels_gpu.py carries that term).
 constexpr int GN_ROWS = 32;
 __global__ __launch_bounds__(256) void gn_stats_kernel(const bf16_t* __restrict__ x, int ldx, const float* __restrict__ add, int ld_add, int HW, int C, int G,
                                                        float* __restrict__ partial) {
@@ -302,7 +308,8 @@ __global__ __launch_bounds__(256) void diffusion_x0_kernel(const float* __restri
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) x0[i] = c0 * sample[i] + c1 * mo[i];
 }
 
-// q-quantile of |x| per row with torch.quantile's linear interpolation: v[lo] + (v[lo + 1] - v[lo]) * frac, pos = q (n - 1).  Non-negative
+// q-quantile of |x| per row with torch.quantile's linear interpolation: v[lo] + (v[hi] - v[lo]) * frac, pos = q (n - 1), hi = ceil(pos): a whole
+// rank interpolates v[lo] with itself and never touches v[lo + 1] (which may be inf: inf * 0 would be NaN where torch gives v[lo]).  Non-negative
 // floats order like their bit patterns: four 8-bit radix passes find the (lo + 1)-th smallest, a fifth pass the smallest value above it
 // (or itself when it repeats).  One workgroup per row.
 __global__ __launch_bounds__(1024) void quantile_abs_kernel(const float* __restrict__ x, long long n, float q, float* __restrict__ out) {
@@ -351,7 +358,7 @@ __global__ __launch_bounds__(1024) void quantile_abs_kernel(const float* __restr
     atomicMin((unsigned*)&s_next, __float_as_uint(nxt));   // non-negative floats: unsigned order = float order
     __syncthreads();
     if (threadIdx.x == 0) {
-        const float vhi = (long long)s_cnt_le > lo + 1 || lo + 1 >= n ? vlo : s_next;
+        const float vhi = frac == 0.f || (long long)s_cnt_le > lo + 1 || lo + 1 >= n ? vlo : s_next;
         out[blockIdx.x] = vlo + (vhi - vlo) * frac;
     }
 }
@@ -394,6 +401,7 @@ extern "C" int fm_unet_im2col(const void* src1, int ld1, int C1, const void* src
     a.src1 = (const bf16_t*)src1; a.src2 = (const bf16_t*)src2; a.out = (bf16_t*)out;
     a.ld1 = ld1; a.ld2 = ld2; a.ldo = ldo; a.B = B; a.H = H; a.W = W; a.C1 = C1; a.C2 = C2; a.H2 = C2 ? H2 : 1; a.W2 = C2 ? W2 : 1;
     a.ksize = ksize; a.stride = stride; a.up1 = up1; a.kpad = kpad;
+    a.sy2 = (float)a.H2 / (float)H; a.sx2 = (float)a.W2 / (float)W;
     const int pad = ksize / 2;
     a.Ho = (H + 2 * pad - ksize) / stride + 1; a.Wo = (W + 2 * pad - ksize) / stride + 1;
     const long long total = (long long)B * a.Ho * a.Wo * (kpad / 8);

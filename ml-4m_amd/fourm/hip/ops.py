@@ -75,7 +75,8 @@ def _ld(t: torch.Tensor) -> int:
 # ---------------------------------------------------------------------------------------------
 # GEMM
 # ---------------------------------------------------------------------------------------------
-# split-K scratch of fm_gemm_nt (fm_gemm_nt_args.splitk_ws): one fp32 buffer per device, shared by every launch (stream order)
+# split-K scratch of fm_gemm_nt (fm_gemm_nt_args.splitk_ws): one fp32 buffer per (device, stream, graph being captured), shared by the
+# launches of that stream in stream order - never across streams or between two captured graphs, which may run at the same time
 SPLITK_MAX_OUT = 128 * 128 * 128          # outputs of up to 128 tiles of 128 x 128 can be split (the kernel decides)
 _SPLITK_WS = {}
 

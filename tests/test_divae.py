@@ -111,6 +111,28 @@ def test_unet_parameter_tree_and_schedulers_match_upstream():
         DiVAE(image_size=32, enc_type="vit_s_enc", patch_size=16, codebook_size=64, latent_dim=8, dec_type="uvit_b_p4_f16")
 
 
+def nearest_index(n_out, n_in):
+    """The second-source index of fm_unet_im2col (csrc/unet.hip im2col_kernel), restated: min(floor(fp32(i) * s), n_in - 1) with
+    s = fp32(n_in) / fp32(n_out), every operation rounded to fp32."""
+    scale = torch.tensor(float(n_in), dtype=torch.float32) / torch.tensor(float(n_out), dtype=torch.float32)
+    return torch.clamp(torch.floor(torch.arange(n_out, dtype=torch.float32) * scale).long(), max=n_in - 1)
+
+
+def test_im2col_nearest_index_formula_is_f_interpolate_for_every_ratio():
+    """The conditioning is brought to the patch grid by F.interpolate(mode="nearest") upstream (unet.py:732).  The index formula the gather
+    kernel evaluates equals it for every pair of sizes up to 64; the integer rule i * n_in // n_out it replaced does not (14 under 46,
+    26 under 44, 30 under 58, ...).  The kernel itself is held to F.interpolate over the same ratios in tests/test_divae_kernels_gpu.py."""
+    differs = []
+    for n_in in range(1, 65):
+        src = torch.arange(n_in, dtype=torch.float32).view(1, 1, n_in, 1)
+        for n_out in range(1, 65):
+            want = torch.nn.functional.interpolate(src, (n_out, 1), mode="nearest").view(-1).long()
+            assert torch.equal(nearest_index(n_out, n_in), want), (n_out, n_in)
+            if not torch.equal(torch.arange(n_out) * n_in // n_out, want):
+                differs.append((n_out, n_in))
+    assert (46, 14) in differs and (56, 14) not in differs
+
+
 # ---- GPU -------------------------------------------------------------------------------------------------------------------------------
 def _small_net():
     from fourm.vq.models.unet import PatchedUNetCondCat
@@ -299,6 +321,7 @@ def test_hip_scheduler_steps_match_upstream_fixture():
             assert e < 2e-5, ("ddpm", pred, thr, clip, t, e)
     print("scheduler steps, worst relative error:", worst)
     # the quantile kernel alone against torch.quantile (ties, a constant row, an odd length)
+    # (q (n - 1) is a whole number for all four q at n = 3001: no interpolation here - tests/test_divae_kernels_gpu.py::test_quantile_abs has the fractional ranks)
     from fourm.hip import _lib as L, ops
     g = torch.Generator().manual_seed(3)
     x = torch.randn(5, 3001, generator=g)
