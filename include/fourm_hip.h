@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define FM_ABI_VERSION 8
+#define FM_ABI_VERSION 9
 int fm_abi_version(void);
 const char* fm_last_error(void);
 
@@ -59,7 +59,11 @@ typedef struct fm_gemm_nt_args {
     const void* W; const void* W2; const void* X;
     void* out; void* out2; const void* res; const void* bias; const void* bias2;
     int32_t M, N, K, ldw, ldx, ldo, ldo2, ldr, Hp, epilogue;
-    const fm_gemm_group* groups; const int32_t* tile_group; int32_t max_N, pad_;
+    const fm_gemm_group* groups; const int32_t* tile_group; int32_t max_N;
+    /* fixed_tiling (ABI 9; dense launches, no conv_*): != 0 pins the launch to ONE kernel and tile configuration (128 x 128 tiles, K-step 32,
+     * no split over K, no few-row kernel) whatever M, N and K are, so that a row of out depends on that row of X alone, bit for bit, however
+     * many rows the call has.  The instance-mask tokenizer runs on it: an instance's tokens and mask must not depend on the batch it came in. */
+    int32_t fixed_tiling;
     /* Row range in DEVICE memory (ABI 7; both or neither, NULL = rows [0, M)): the launch covers rows [*row0_dev, *row0_dev +
      * roundup(*m_dev, FM_SEG_ROWS)) of X / out - one modality head's segment as fm_segment_rows laid it out (seg_start[h], seg_count[h];
      * pad rows zero) - with M an upper bound.  One dense launch per head then replaces the grouped launch without a host read of the
@@ -440,6 +444,14 @@ int fm_l2norm_rows(const void* x, int ldx, void* y, int ldy, int R, int D, void*
 int fm_vq_assign(const void* z, int ldz, const void* codes_normalized, const void* embed, int K, int D, int R,
                  int tokens_per_image, int normalize_latents, void* ws_val, void* ws_idx, int splits, int64_t* tokens,
                  void* quant, void* stream);
+/* The same search for any latent width (SAM-instance tokenizer: latent_dim 1024; replaces l2norm(z) @ l2norm(embed).T, argmax and
+ * embed[ind] of CosineSimCodebook.forward, quantize_lucid.py:388-407, without the (R, K) score matrix).  z: f32 (R, ldz), always
+ * l2-normalised in-kernel; codes_normalized / embed: f32 (K, D) contiguous; z and codes_normalized 16-byte aligned.  Exact fp32
+ * scores (v_mfma_f32_32x32x2_f32: one fmaf chain over d), lowest index on equal scores.  D % 4 == 0, 8 <= D <= 4096, ldz % 4 == 0.
+ * ws_val / ws_idx: (R, code_tiles) f32 / int32 scratch, code_tiles = ceil(K / FM_VQ_WIDE_TILE).  tokens, quant: as fm_vq_assign. */
+#define FM_VQ_WIDE_TILE 128
+int fm_vq_assign_wide(const void* z, int ldz, const void* codes_normalized, const void* embed, int K, int D, int R,
+                      int tokens_per_image, void* ws_val, void* ws_idx, int code_tiles, int64_t* tokens, void* quant, void* stream);
 /* Codebook training statistics (CosineSimCodebook.forward, training branch, quantize_lucid.py:409-419): bins[k] = number of
  * latents assigned to code k, sums[k][:] = sum of those latents after L2 normalisation.  z: f32 (R, ldz); tokens: int64 (R);
  * bins f32 (K), sums f32 (K, D): zeroed here, accumulated with fp32 atomics.  With a synchronised codebook the caller all-reduces
@@ -474,6 +486,15 @@ int fm_vq_ema_update_euclid(const void* bins, const void* sums, void* embed, voi
  *   fm_tanh_bwd_f32: dx = dy * (1 - t * t) on f32 (R, N) tiles of row stride ld (Mlp with act_layer = Tanh, vit_models.py:494-496)
  *   fm_embed_rows_f32: out[r] = table[idx[r]] (f32 rows; F.embedding) */
 int fm_vq_unpatchify(const void* rows, int ld_rows, void* img, int B, int C, int H, int W, int P, void* stream);
+/* One ConvNeXt block of ViTDecoder(out_conv=True) (vit_models.py:298-335; two of them follow the unpatchify, :655-657) in one launch:
+ *   y = x + gamma * pwconv2(GELU(pwconv1(LayerNorm_C(dwconv7x7(x)))))
+ * replaces Conv2d(C, C, 7, padding=3, groups=C) -> permute -> LayerNorm(C) -> Linear(C, 4C) -> GELU (erf) -> Linear(4C, C) -> gamma * . ->
+ * permute -> residual add.  x, y: f32 (B, C, H, W), y != x;  dw_weight (C, 1, 7, 7), dw_bias (C), ln_weight / ln_bias (C),
+ * pw1_weight (4C, C), pw1_bias (4C), pw2_weight (C, 4C), pw2_bias (C), gamma (C): f32.  1 <= C <= FM_CONVNEXT_MAX_C. */
+#define FM_CONVNEXT_MAX_C 4
+int fm_convnext_block(const void* x, void* y, const void* dw_weight, const void* dw_bias, const void* ln_weight, const void* ln_bias,
+                      const void* pw1_weight, const void* pw1_bias, const void* pw2_weight, const void* pw2_bias, const void* gamma,
+                      int B, int C, int H, int W, float eps, void* stream);
 int fm_vq_latent_grad(const void* z, int ldz, const void* embed, const int64_t* tokens, const void* dquant, int ld_dquant, const void* grad_loss,
                       float commitment_weight, void* dz, int ld_dz, void* commit_value, int R, int D, void* stream);
 int fm_tanh_bwd_f32(const void* dy, const void* t, void* dx, int R, int N, int ld, void* stream);

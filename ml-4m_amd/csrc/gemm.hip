@@ -1232,7 +1232,7 @@ int launch_nt(const NTArgs& a, int max_n, hipStream_t s) {
         }
         return launch_nt_cfg<128, 256, 2, 4, 32, 3, EPI, true>(a, max_n, s);
     }
-    if (a.M <= 128) return launch_nt_cfg<128, 128, 2, 2, 32, 3, EPI, GROUPED>(a, max_n, s);
+    if (a.M <= 128 || a.fixed_tiling) return launch_nt_cfg<128, 128, 2, 2, 32, 3, EPI, GROUPED>(a, max_n, s);
     if constexpr (!GROUPED) {
         int cfg = g_nt_config;
         if (cfg == 9) {  // epilogues that READ and long reductions: one workgroup per CU (10); SwiGLU: 256 x 256 tiles (12)
@@ -1283,6 +1283,9 @@ extern "C" int fm_gemm_nt(const fm_gemm_nt_args* p, void* stream) {
     a.dephase_groups = g_lab[0]; a.dephase_step = g_lab[1]; a.lab = g_lab[3];
     hipStream_t s = (hipStream_t)stream;
     a.m_dev = p->m_dev; a.row0_dev = p->row0_dev;
+    const bool fixed = p->fixed_tiling != 0;      // one kernel, one tile configuration: none of the shape-dependent routes below
+    FM_CHECK_ARG(!fixed || (!grouped && !p->m_dev && !p->row0_dev && p->conv_C == 0), "fm_gemm_nt: fixed_tiling is for dense launches (no groups, device-side rows or conv_*)");
+    a.fixed_tiling = fixed ? 1 : 0;
     if (p->m_dev || p->row0_dev) {            // row range in device memory (one dense launch per modality head): gemm_nt3 only
         FM_CHECK_ARG(p->m_dev && p->row0_dev && !grouped, "fm_gemm_nt: m_dev and row0_dev go together (dense launches only)");
         const int r = fm_launch_nt3(a, p->epilogue, g_lab[2] ? g_lab[2] : 3, s);
@@ -1293,7 +1296,7 @@ extern "C" int fm_gemm_nt(const fm_gemm_nt_args* p, void* stream) {
         return -1;
     }
     const int max_n = grouped ? p->max_N : p->N;
-    if (!grouped && p->M <= 32 && p->conv_C == 0) {             // a handful of rows (a decoding step): the weight-streaming kernel of gemm_skinny.hip
+    if (!grouped && p->M <= 32 && p->conv_C == 0 && !fixed) {             // a handful of rows (a decoding step): the weight-streaming kernel of gemm_skinny.hip
         const int r = fm_launch_nt_skinny(a, p->epilogue, s);
         if (r < 0) { fm_set_error("fm_gemm_nt (skinny): launch failed"); return -2; }
         if (r > 0) return 0;
@@ -1335,7 +1338,7 @@ extern "C" int fm_gemm_nt(const fm_gemm_nt_args* p, void* stream) {
     // (the convolutions of the DiVAE UNet: M = batch x 56^2 ... batch x 7^2 rows, N = 256 / 512, K up to 9216) runs on 128 x 128 tiles; when
     // even those leave half of the chip idle and the reduction is long, K is cut into slices on gridDim.y (fp32 partial tiles in the caller's
     // scratch, fm_gemm_nt_args.splitk_ws) and one reduction pass adds the bias and rounds: M = 392, N = 512, K = 4608: 64 -> ~15 us.
-    if (!grouped && g_lab[9] && p->epilogue == FM_EPI_BF16 && p->M > 32 && !p->out2 && !p->res && p->N % 4 == 0 && (((uintptr_t)p->out) & 7) == 0) {
+    if (!grouped && !fixed && g_lab[9] && p->epilogue == FM_EPI_BF16 && p->M > 32 && !p->out2 && !p->res && p->N % 4 == 0 && (((uintptr_t)p->out) & 7) == 0) {
         const int cus = n_compute_units();
         const long t256 = (long)((p->M + 255) / 256) * ((p->N + 255) / 256);
         if (t256 * 2 <= cus) {
@@ -1365,17 +1368,17 @@ extern "C" int fm_gemm_nt(const fm_gemm_nt_args* p, void* stream) {
             return launch_nt_cfg<128, 128, 2, 2, 32, 3, EPI_BF16, false>(a, max_n, s);
         }
     }
-    if (!grouped && g_lab[4]) {               // the 4-wave 256 x 384-tile kernel (gemm_nt4.hip) takes the plain bf16 launches it tiles exactly
+    if (!grouped && !fixed && g_lab[4]) {               // the 4-wave 256 x 384-tile kernel (gemm_nt4.hip) takes the plain bf16 launches it tiles exactly
         const int r = fm_launch_nt4(a, p->epilogue, g_lab[4], s);
         if (r < 0) { fm_set_error("fm_gemm_nt (nt4): launch failed"); return -2; }
         if (r > 0) return 0;
     }
-    if (!grouped && g_lab[2]) {               // the lock-step large-tile kernel (gemm_nt3.hip) takes the dense launches it handles
+    if (!grouped && !fixed && g_lab[2]) {               // the lock-step large-tile kernel (gemm_nt3.hip) takes the dense launches it handles
         const int r = fm_launch_nt3(a, p->epilogue, g_lab[2], s);
         if (r < 0) { fm_set_error("fm_gemm_nt (nt3): launch failed"); return -2; }
         if (r > 0) return 0;
     }
-    if (!grouped && g_nt_config == 9) {       // the flattened persistent kernel takes the big dense launches it handles
+    if (!grouped && !fixed && g_nt_config == 9) {       // the flattened persistent kernel takes the big dense launches it handles
         const int r = fm_launch_nt_flat(a, p->epilogue, s);
         if (r < 0) { fm_set_error("fm_gemm_nt (flat): launch failed"); return -2; }
         if (r > 0) return 0;

@@ -24,6 +24,7 @@ struct NTArgs {
     // in[b][oy * stride + tap / 3 - 1][ox * stride + tap % 3 - 1][c] (zero outside the (conv_H, conv_W) grid) - fm_unet_im2col's rows without the round trip
     int conv_C, conv_H, conv_W, conv_Ho, conv_Wo, conv_stride, conv_up;
     int split_k, k_slice; long long split_stride;         // gemm_nt_kernel with FM_EPI_F32 on gridDim.y = split_k K-slices of k_slice elements: slice z writes fp32 partials at out + z * split_stride
+    int fixed_tiling;                                     // fm_gemm_nt_args.fixed_tiling: one tile configuration whatever the shape (row results independent of M)
     int lab;                                              // experiment flags of gemm_nt3 (fm_lab_set 3): 1 no wait for the DMA, 2 no DMA, 4 no stores, 16 all DMA pieces in one k-step, 256 take the residual epilogue
 };
 

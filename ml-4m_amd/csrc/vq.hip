@@ -207,6 +207,140 @@ extern "C" int fm_vq_assign_bias(const void* z, int ldz, const void* codes_norma
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The same cosine search for any latent width (SAM-instance tokenizer: latent_dim = 1024, 1024 codes; quantize_lucid.py:388-407).
+// A lane cannot hold a wide latent row, so the scores are a tiled fp32 product on v_mfma_f32_32x32x2_f32 (exact fp32: one fmaf chain
+// over d per score, like gemm_f32_mfma_kernel in fp32_verify.hip) whose (rows x codes) matrix never leaves the registers: a block owns
+// 128 codes x 128 latent rows, the codes are the MFMA row operand, so a lane ends up with 2 x 16 codes of ONE latent row per 32 x 32
+// tile and reduces them in ascending code order; lane halves, then the two waves that share the rows, are merged with the lowest
+// index winning on equal scores.  Per block and row one (best score, lowest best index) goes to ws_val / ws_idx (R, ceil(K / 128));
+// vq_merge_kernel picks across the code tiles (ascending) and gathers quant.  Latent rows are l2-normalised while they are staged.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+__global__ __launch_bounds__(256) void vq_search_wide_kernel(const float* __restrict__ z, int ldz, const float* __restrict__ En, int K, int D,
+                                                             int R, float* __restrict__ best_val, int* __restrict__ best_idx) {
+    constexpr int T = FM_VQ_WIDE_TILE, KS = 32, LDT = KS + 1;          // row stride 33 floats: the 32 lanes of a half-wave hit 32 banks
+    __shared__ float Es[T * LDT], Zs[T * LDT];
+    __shared__ float inv[T];
+    __shared__ float rv[2][T];
+    __shared__ int ri[2][T];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int ww = wave >> 1, wx = wave & 1;
+    const int n0 = blockIdx.x * T, m0 = blockIdx.y * T;
+    // 1 / max(|z_r|, 1e-12) of the block's rows (F.normalize): a wave per row, float4 per lane
+    for (int r = wave; r < T; r += 4) {
+        const float* zr = z + (size_t)(m0 + r < R ? m0 + r : R - 1) * ldz;
+        float s = 0.f;
+        for (int d = lane * 4; d < D; d += 256) {
+            const float4 v = *(const float4*)(zr + d);
+            s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+        }
+        s = wave_sum(s);
+        if (lane == 0) inv[r] = 1.0f / fmaxf(sqrtf(s), 1e-12f);
+    }
+    __syncthreads();
+    f32x16_t acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    // staging: thread -> (row = tid / 8 + 32 p, 4 floats at column (tid % 8) * 4); rows past the edge repeat the last one (never reported)
+    const int lr = threadIdx.x >> 3, lc = (threadIdx.x & 7) * 4;
+    const float* ep[4]; const float* zp[4];
+    float zi[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const int r = lr + 32 * p;
+        ep[p] = En + (size_t)(n0 + r < K ? n0 + r : K - 1) * D + lc;
+        zp[p] = z + (size_t)(m0 + r < R ? m0 + r : R - 1) * ldz + lc;
+        zi[p] = inv[r];
+    }
+    float4 ereg[4], zreg[4];
+    auto load = [&](int k0) {
+        const bool in = k0 + lc < D;                       // D % 4 == 0: a float4 is inside or outside as a whole
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            ereg[p] = in ? *(const float4*)(ep[p] + k0) : make_float4(0.f, 0.f, 0.f, 0.f);
+            zreg[p] = in ? *(const float4*)(zp[p] + k0) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    };
+    auto stash = [&]() {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            float* ed = Es + (lr + 32 * p) * LDT + lc; float* zd = Zs + (lr + 32 * p) * LDT + lc;
+            ed[0] = ereg[p].x; ed[1] = ereg[p].y; ed[2] = ereg[p].z; ed[3] = ereg[p].w;
+            zd[0] = zreg[p].x * zi[p]; zd[1] = zreg[p].y * zi[p]; zd[2] = zreg[p].z * zi[p]; zd[3] = zreg[p].w * zi[p];
+        }
+    };
+    load(0);
+    for (int k0 = 0; k0 < D; k0 += KS) {
+        __syncthreads();                       // the previous step's readers are done
+        stash();
+        __syncthreads();
+        if (k0 + KS < D) load(k0 + KS);        // next step in flight under the MFMAs
+        const float* eb = Es + (ww * 64 + (lane & 31)) * LDT + (lane >> 5);
+        const float* zb = Zs + (wx * 64 + (lane & 31)) * LDT + (lane >> 5);
+#pragma unroll
+        for (int kk = 0; kk < KS; kk += 2) {
+            const float a0 = eb[kk], a1 = eb[32 * LDT + kk], b0 = zb[kk], b1 = zb[32 * LDT + kk];
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+        }
+    }
+    // accumulator map: column (lane & 31) = latent row, register 4 g + e = code 8 g + 4 (lane >> 5) + e of the 32-code tile
+    const int fhi = lane >> 5;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        float bv = -INFINITY;
+        int bi = n0;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {              // ascending code index: strict > keeps the first maximum
+                    const int n = n0 + ww * 64 + i * 32 + 8 * g + 4 * fhi + e;
+                    const float v = acc[i][j][4 * g + e];
+                    if (n < K && v > bv) { bv = v; bi = n; }
+                }
+        const float ov = __shfl_xor(bv, 32, 64);
+        const int oi = __shfl_xor(bi, 32, 64);
+        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        if (lane < 32) { rv[ww][wx * 64 + j * 32 + lane] = bv; ri[ww][wx * 64 + j * 32 + lane] = bi; }
+    }
+    __syncthreads();
+    if (threadIdx.x < T && m0 + threadIdx.x < R) {
+        const int t = threadIdx.x;
+        const bool second = rv[1][t] > rv[0][t];           // the second wave pair holds the higher code indices: strict
+        best_val[(size_t)(m0 + t) * gridDim.x + blockIdx.x] = second ? rv[1][t] : rv[0][t];
+        best_idx[(size_t)(m0 + t) * gridDim.x + blockIdx.x] = second ? ri[1][t] : ri[0][t];
+    }
+}
+
+}  // namespace
+
+extern "C" int fm_vq_assign_wide(const void* z, int ldz, const void* codes_normalized, const void* embed, int K, int D, int R,
+                                 int tokens_per_image, void* ws_val, void* ws_idx, int code_tiles, int64_t* tokens, void* quant, void* stream) {
+    FM_CHECK_ARG(z && codes_normalized && embed && ws_val && ws_idx && tokens, "fm_vq_assign_wide: null pointer");
+    FM_CHECK_ARG(D % 4 == 0 && D >= 8 && D <= 4096, "fm_vq_assign_wide: latent_dim=%d unsupported (a multiple of 4 in [8, 4096])", D);
+    FM_CHECK_ARG(K > 0 && R > 0 && tokens_per_image > 0 && ldz % 4 == 0 && ldz >= D, "fm_vq_assign_wide: bad shape (K, R > 0; ldz %% 4 == 0, ldz >= latent_dim)");
+    FM_CHECK_ARG(((((uintptr_t)z | (uintptr_t)codes_normalized)) & 15) == 0, "fm_vq_assign_wide: z and codes_normalized must be 16-byte aligned");
+    const int tiles = (K + FM_VQ_WIDE_TILE - 1) / FM_VQ_WIDE_TILE;
+    FM_CHECK_ARG(code_tiles == tiles, "fm_vq_assign_wide: code_tiles=%d, expected ceil(K / %d) = %d (the scratch row length)", code_tiles, FM_VQ_WIDE_TILE, tiles);
+    FM_CHECK_ARG((R + FM_VQ_WIDE_TILE - 1) / FM_VQ_WIDE_TILE <= 65535, "fm_vq_assign_wide: too many rows (R=%d)", R);
+    hipLaunchKernelGGL(vq_search_wide_kernel, dim3(tiles, (R + FM_VQ_WIDE_TILE - 1) / FM_VQ_WIDE_TILE), dim3(256), 0, (hipStream_t)stream, (const float*)z, ldz,
+                       (const float*)codes_normalized, K, D, R, (float*)ws_val, (int*)ws_idx);
+    hipLaunchKernelGGL(vq_merge_kernel, dim3((R + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)ws_val, (const int*)ws_idx, tiles,
+                       (const float*)embed, (long long*)tokens, (float*)quant, R, D, tokens_per_image);
+    FM_CHECK_LAUNCH("fm_vq_assign_wide");
+    return 0;
+}
+
 static int vq_code_stats_impl(const void* z, int ldz, const int64_t* tokens, int R, int D, int K, void* bins, void* sums, int normalize, void* stream);
 extern "C" int fm_vq_code_stats(const void* z, int ldz, const int64_t* tokens, int R, int D, int K, void* bins, void* sums, void* stream) {
     return vq_code_stats_impl(z, ldz, tokens, R, D, K, bins, sums, 1, stream);

@@ -1,6 +1,8 @@
 """Thin torch-tensor front end over the C ABI: pointer extraction, shape checks, stream plumbing.
 torch is used here for device memory and streams only; every computation is a HIP kernel."""
+import contextlib
 import ctypes as C
+import threading
 from typing import Optional
 
 import torch
@@ -93,6 +95,21 @@ def _splitk_ws(device):
     return t
 
 
+_TILING = threading.local()
+
+
+@contextlib.contextmanager
+def fixed_tiling(on=True):
+    """Inside the block every dense gemm_nt of this thread runs on ONE kernel and tile configuration (fm_gemm_nt_args.fixed_tiling): a row of
+    the result then depends on that row of x alone, bit for bit, whatever the number of rows - slower on large shapes, batch-invariant."""
+    prev = getattr(_TILING, "fixed", False)
+    _TILING.fixed = bool(on) or prev
+    try:
+        yield
+    finally:
+        _TILING.fixed = prev
+
+
 def gemm_nt(x, w, out, *, epilogue=L.EPI_BF16, bias=None, res=None, w2=None, bias2=None, out2=None, Hp=0, N=None, K=None, M=None, conv=None):
     """out[m][n] = sum_k x[m][k] w[n][k] (+ epilogue).  x: bf16 (M, >=K); w: bf16 (N, >=K).
     fp32 operands select the verification kernel (any strides for w).
@@ -113,7 +130,9 @@ def gemm_nt(x, w, out, *, epilogue=L.EPI_BF16, bias=None, res=None, w2=None, bia
     if conv is not None:
         a.conv_C, a.conv_H, a.conv_W, a.conv_Ho, a.conv_Wo = conv["C"], conv["H"], conv["W"], conv["Ho"], conv["Wo"]
         a.conv_stride, a.conv_up = conv.get("stride", 1), conv.get("up", 0)
-    if epilogue == L.EPI_BF16 and a.M * a.N <= SPLITK_MAX_OUT and a.K >= 512:       # (only launches that can be split need the scratch)
+    if conv is None and getattr(_TILING, "fixed", False):
+        a.fixed_tiling = 1
+    elif epilogue == L.EPI_BF16 and a.M * a.N <= SPLITK_MAX_OUT and a.K >= 512:       # (only launches that can be split need the scratch)
         ws = _splitk_ws(x.device)
         a.splitk_ws, a.splitk_ws_bytes = ws.data_ptr(), ws.numel() * 4
     two = 2 if epilogue == L.EPI_SWIGLU else 1

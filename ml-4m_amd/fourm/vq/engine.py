@@ -204,6 +204,7 @@ def _assign(vq, eng, z, R, G, B, nh, nw, want_quant):
     cb = vq.quantize._codebook
     K = cb.embed.shape[0]
     if getattr(cb, "euclidean", False):
+        _check_search(vq)
         if not cb.is_initted():                             # kmeans_init=True: the first batch initialises the codebook (quantize_lucid.py:271)
             cb.init_embed_(z[:R], normalize=bool(vq.quantize.norm_latents))
         # Euclidean codebook (norm_codes=False): arg-max of <z, e> - |e|^2 / 2 over the raw codes; norm_latents normalises z first (:525-527)
@@ -215,7 +216,10 @@ def _assign(vq, eng, z, R, G, B, nh, nw, want_quant):
         L.check(L.vq_assign_bias(ops._p(z), z.stride(0), ops._p(cb.embed), ops._p(cb.code_bias()), ops._p(cb.embed), K, Ld, R, G,
                                  1 if vq.quantize.norm_latents else 0, ops._p(wv), ops._p(wi), splits, ops._p(tokens), ops._p(quant), ops._stream()))
         return (tokens, quant) if want_quant else tokens
+    wide = Ld != 32                                         # fm_vq_assign holds a 32-wide latent row in registers; any other width: the tiled search
     if not cb.is_initted():                                 # kmeans_init=True: the first batch initialises the codebook (quantize_lucid.py:394)
+        if wide:
+            raise NotImplementedError(f"kmeans_init with latent_dim={Ld}: the k-means kernels are built for latent_dim 32")
         cb.init_embed_(z[:R])
     # ONE buffer of l2-normalised codes, recomputed in place when the codebook changed (in training mode every encode() moves the
     # codebook: a cache keyed on its version would keep every past copy alive)
@@ -227,11 +231,16 @@ def _assign(vq, eng, z, R, G, B, nh, nw, want_quant):
     if slot[0] != stamp:
         L.check(L.l2norm_rows(ops._p(cb.embed), cb.embed.stride(0), ops._p(en), en.stride(0), K, Ld, ops._stream()))
         slot[0] = stamp
-    splits = max(1, min(16, K // 1024))
+    splits = -(-K // L.VQ_WIDE_TILE) if wide else max(1, min(16, K // 1024))
     wv = ws.get("vq.wv", (R, splits), torch.float32)
     wi = ws.get("vq.wi", (R, splits), torch.int32)
     tokens = torch.empty(B, nh, nw, dtype=torch.int64, device=z.device)
     quant = torch.empty(B, Ld, nh, nw, dtype=torch.float32, device=z.device) if want_quant else None
+    if wide:
+        # exact-fp32 MFMA tiles of (128 rows x 128 codes), reduced to (best score, lowest index) per tile in the epilogue: no (R, K) matrix
+        L.check(L.vq_assign_wide(ops._p(z), z.stride(0), ops._p(en), ops._p(cb.embed), K, Ld, R, G, ops._p(wv), ops._p(wi), splits,
+                                 ops._p(tokens), ops._p(quant), ops._stream()))
+        return (tokens, quant) if want_quant else tokens
     # cosine similarity normalises the latents (quantize_lucid.py:394-395); norm_latents only moves that
     # normalisation in front of the (training-time) commitment loss
     L.check(L.vq_assign(ops._p(z), z.stride(0), ops._p(en), ops._p(cb.embed), K, Ld, R, G, 1, ops._p(wv), ops._p(wi), splits,
@@ -239,8 +248,28 @@ def _assign(vq, eng, z, R, G, B, nh, nw, want_quant):
     return (tokens, quant) if want_quant else tokens
 
 
+def _check_search(vq):
+    """Refuse a codebook the search kernels cannot serve BEFORE the encoder runs."""
+    if getattr(vq.quantize._codebook, "euclidean", False) and vq.latent_dim != 32:
+        raise NotImplementedError(f"Euclidean codebook (norm_codes=False) with latent_dim={vq.latent_dim}: fm_vq_assign_bias is built for latent_dim 32 "
+                                  "(the wide search, fm_vq_assign_wide, is cosine only)")
+
+
+def _batch_invariant(vq):
+    """Instance-mask tokenizers (latent_dim > 64 / out_conv: the inference-only configurations) are called with however many instances an
+    image has (upstream's decode_sam_instances reshapes them into the batch): their GEMMs run on one fixed tiling, so that an instance's
+    tokens and mask are the same bits whatever batch it came in.  Every other kernel of the path is row- or sample-local already."""
+    return ops.fixed_tiling(vq._inference_only() is not None)
+
+
 @torch.no_grad()
 def vq_encode(vq, x):
+    _check_search(vq)
+    with _batch_invariant(vq):
+        return _vq_encode(vq, x)
+
+
+def _vq_encode(vq, x):
     enc = vq.encoder
     eng, stream, (B, nh, nw) = _tokens(enc, x, prep=vq._prep())
     ws, D, Ld = eng.ws, eng.D, vq.latent_dim
@@ -270,9 +299,14 @@ def _quant_rows(vq, tokens, dev):
 
 def _decode_rows(vq, q_rows, B, nh, nw, st=None):
     """Quantised rows (R, latent_dim) f32 -> image (B, C, H, W) f32 through post_quant_proj, the decoder blocks and out_proj."""
+    if hasattr(vq.decoder, "out_conv") and st is not None:
+        raise NotImplementedError("ViTDecoder with out_conv=True is inference only: the ConvNeXt blocks have no backward kernel")
+    with _batch_invariant(vq):
+        return _decode_rows_impl(vq, q_rows, B, nh, nw, st)
+
+
+def _decode_rows_impl(vq, q_rows, B, nh, nw, st):
     dec = vq.decoder
-    if hasattr(dec, "out_conv"):
-        raise NotImplementedError("ViTDecoder with out_conv=True has no HIP path")
     eng = _engine(dec)
     ws, D, Ld = eng.ws, eng.D, vq.latent_dim
     G, R = nh * nw, B * nh * nw
@@ -296,6 +330,15 @@ def _decode_rows(vq, q_rows, B, nh, nw, st=None):
     ops.gemm_nt(xb, eng.w(dec.out_proj.weight), rows, epilogue=L.EPI_F32, bias=dec.out_proj.bias, M=R, N=Fo, K=D)
     img = torch.empty(B, C, nh * P, nw * P, dtype=f32, device=q_rows.device)
     L.check(L.vq_unpatchify(ops._p(rows), rows.stride(0), ops._p(img), B, C, nh * P, nw * P, P, ops._stream()))
+    if hasattr(dec, "out_conv"):
+        # two ConvNeXt blocks on the assembled image (vit_models.py:655-657), one launch each, fp32: img -> mid -> out
+        H, W = nh * P, nw * P
+        mid, out = ws.get("dec.conv", (B, C, H, W), f32), torch.empty_like(img)
+        for blk, src, dst in zip(dec.out_conv, (img, mid), (mid, out)):
+            L.check(L.convnext_block(ops._p(src), ops._p(dst), *(ops._p(t.detach()) for t in (
+                blk.dwconv.weight, blk.dwconv.bias, blk.norm.weight, blk.norm.bias, blk.pwconv1.weight, blk.pwconv1.bias, blk.pwconv2.weight,
+                blk.pwconv2.bias, blk.gamma)), B, C, H, W, blk.norm.eps, ops._stream()))
+        img = out
     if st is not None:
         st.update(xb=xb, x_final=stream)
     return img

@@ -121,6 +121,31 @@ def _init_vit_weights(mod):
             nn.init.constant_(m.weight, 1.0)
 
 
+CONVNEXT_MAX_CHANNELS = 4      # fm_convnext_block keeps a pixel's pointwise MLP in registers (FM_CONVNEXT_MAX_C)
+
+
+class ConvNeXtBlock(nn.Module):
+    """Parameter owner of one ConvNeXt block in upstream's layout (vit_models.py:298-335): depthwise 7 x 7 convolution, LayerNorm over
+    the channels, Linear(dim, 4 dim), GELU, Linear(4 dim, dim), layer scale ``gamma``, residual.  Computed by fm_convnext_block inside
+    ``fourm.vq.engine`` (one launch per block)."""
+
+    def __init__(self, dim, drop_path=0., layer_scale_init_value=1e-6):
+        super().__init__()
+        if drop_path:
+            raise NotImplementedError("stochastic depth is not implemented in the HIP tokenizer path")
+        if not layer_scale_init_value > 0:
+            raise NotImplementedError("ConvNeXtBlock without layer scale (layer_scale_init_value <= 0) is not implemented")
+        self.dwconv = nn.Conv2d(dim, dim, kernel_size=7, padding=3, groups=dim)
+        self.norm = nn.LayerNorm(dim, eps=1e-6)
+        self.pwconv1 = nn.Linear(dim, 4 * dim)
+        self.act = nn.GELU()
+        self.pwconv2 = nn.Linear(4 * dim, dim)
+        self.gamma = nn.Parameter(layer_scale_init_value * torch.ones(dim), requires_grad=True)
+
+    def forward(self, x):
+        raise RuntimeError("ConvNeXtBlock computes inside VQVAE.decode_quant / decode_tokens (fourm.vq.engine); it has no stand-alone forward")
+
+
 class ViTDecoder(nn.Module):
     """(B, dim_tokens, N_H, N_W) latent features -> (B, out_channels, H, W) images.  Same constructor as upstream (:528-546); the
     arithmetic runs in ``fourm.vq.engine`` (blocks on the trunk kernels, out_proj + patch re-assembly)."""
@@ -130,8 +155,9 @@ class ViTDecoder(nn.Module):
                  drop_path_rate: float = 0.0, norm_layer: nn.Module = partial(nn.LayerNorm, eps=1e-6), sincos_pos_emb: bool = True,
                  learnable_pos_emb: bool = False, patch_proj: bool = True, post_mlp: bool = False, out_conv: bool = False, **ignore_kwargs):
         super().__init__()
-        if out_conv:
-            raise NotImplementedError("out_conv=True (ConvNeXt blocks behind the decoder) has no HIP path")
+        if out_conv and out_channels > CONVNEXT_MAX_CHANNELS:
+            raise NotImplementedError(f"out_conv=True with out_channels={out_channels}: the ConvNeXt kernel (fm_convnext_block) is built for at most "
+                                      f"{CONVNEXT_MAX_CHANNELS} channels")
         self.out_channels, self.dim_tokens, self.patch_proj = out_channels, dim_tokens, patch_proj
         self.P_H, self.P_W = pair(patch_size)
         self.H, self.W = pair(resolution)
@@ -148,6 +174,8 @@ class ViTDecoder(nn.Module):
             self.norm_mlp = norm_layer(dim_tokens)
             self.post_mlp = Mlp(dim_tokens, int(mlp_ratio * dim_tokens), act_layer=nn.Tanh)
         self.out_proj = nn.Linear(dim_tokens, out_channels * self.P_H * self.P_W if patch_proj else out_channels)
+        if out_conv:          # two ConvNeXt blocks on the assembled image against patch seams (vit_models.py:583-584); inference only
+            self.out_conv = nn.Sequential(ConvNeXtBlock(dim=out_channels), ConvNeXtBlock(dim=out_channels))
         _init_vit_weights(self)
 
     def get_num_layers(self) -> int:

@@ -111,8 +111,19 @@ class VQ(nn.Module, PyTorchModelHubMixin):
         with torch.no_grad():
             return self._encode(x)
 
+    def _inference_only(self):
+        """Why this configuration cannot train here (None: it can).  Checked in Python before any kernel is launched."""
+        if self.latent_dim > 64:
+            return (f"latent_dim={self.latent_dim} is inference only: the codebook statistics, EMA update and latent gradient kernels "
+                    "(fm_vq_code_stats, fm_vq_ema_update, fm_vq_latent_grad*) are built for latent_dim <= 64")
+        if hasattr(getattr(self, "decoder", None), "out_conv"):
+            return "a decoder with out_conv=True is inference only: the ConvNeXt blocks (fm_convnext_block) have no backward kernel"
+        return None
+
     def _encode(self, x):
         from .engine import vq_encode
+        if self.training and self.quantize.training and self._inference_only():
+            raise NotImplementedError(f"training-mode quantizer (EMA codebook update): {self._inference_only()}; call .eval()")
         quant, loss, tokens = vq_encode(self, self.prepare_input(x))
         if self.training and self.quantize.training:
             # upstream's training-mode quantizer: EMA codebook update + the commitment term's VALUE (quantize_lucid.py:409-426, :540-548)
@@ -174,6 +185,9 @@ class VQVAE(VQ):
         from .engine import VQVAEStep, vqvae_train_forward
         x = self.prepare_input(x)
         needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if (needs_grad or self.training) and self._inference_only():      # (training mode without gradients still takes the training forward: commitment value, EMA update)
+            raise NotImplementedError(f"VQVAE.forward in training mode or with gradients enabled: {self._inference_only()}; "
+                                      "call .eval() and run under torch.no_grad()")
         if needs_grad:
             # the autograd anchor is a parameter that DOES require grad (post_quant_proj may be frozen while the encoder or decoder trains)
             anchor = next(p for p in self.parameters() if p.requires_grad)
