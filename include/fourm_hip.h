@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define FM_ABI_VERSION 9
+#define FM_ABI_VERSION 10
 int fm_abi_version(void);
 const char* fm_last_error(void);
 
@@ -452,6 +452,16 @@ int fm_vq_assign(const void* z, int ldz, const void* codes_normalized, const voi
 #define FM_VQ_WIDE_TILE 128
 int fm_vq_assign_wide(const void* z, int ldz, const void* codes_normalized, const void* embed, int K, int D, int R,
                       int tokens_per_image, void* ws_val, void* ws_idx, int code_tiles, int64_t* tokens, void* quant, void* stream);
+/* Memcodes code search (multi-head inner-product codebook of the pose / global-feature tokenizers; replaces the eval branch of
+ * Memcodes.forward, quantize_memcodes.py:84-109: logits = einsum(q, k), argmax, one_hot, einsum(attn, v), without the (R, K) score matrix).
+ * z: f32 (R, ldz), head h reads columns [h d, (h + 1) d); keys, values: f32 (H, K, d) contiguous (to_k / to_v applied to the codes); row
+ * r = b tokens_per_image + g.  tokens[(b H + h) tokens_per_image + g] = lowest index of the largest fp32 score <z_h, keys[h][j]> (exact fp32,
+ * one fmaf chain over d per score; NO normalisation; upstream's d^-0.5 factor on the query is left out: a positive scale cannot change an
+ * arg-max).  quant (optional): f32 (B, H d, tokens_per_image), quant[b][h d + c][g] = values[h][token][c].  d % 4 == 0, 8 <= d <= 4096,
+ * H, K, R >= 1, ldz % 4 == 0, ldz >= H d, z and keys 16-byte aligned, at most 65535 heads and 65535 row tiles of FM_VQ_WIDE_TILE rows.
+ * ws_val / ws_idx: (H, R, code_tiles) f32 / int32 scratch, code_tiles = ceil(K / FM_VQ_WIDE_TILE). */
+int fm_memcodes_assign(const void* z, int ldz, const void* keys, const void* values, int K, int d, int H, int R,
+                       int tokens_per_image, void* ws_val, void* ws_idx, int code_tiles, int64_t* tokens, void* quant, void* stream);
 /* Codebook training statistics (CosineSimCodebook.forward, training branch, quantize_lucid.py:409-419): bins[k] = number of
  * latents assigned to code k, sums[k][:] = sum of those latents after L2 normalisation.  z: f32 (R, ldz); tokens: int64 (R);
  * bins f32 (K), sums f32 (K, D): zeroed here, accumulated with fp32 atomics.  With a synchronised codebook the caller all-reduces

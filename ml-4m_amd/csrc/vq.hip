@@ -218,6 +218,9 @@ extern "C" int fm_vq_assign_bias(const void* z, int ldz, const void* codes_norma
 // ------------------------------------------------------------------------------------------------
 namespace {
 
+// MEM (fm_memcodes_assign, below): blockIdx.z is a head that reads columns [h D, (h + 1) D) of z and its own (K, D) block of En, rows are
+// NOT normalised (plain inner products), and the winners go to the head's own (R, code tiles) block of best_val / best_idx.
+template <bool MEM>
 __global__ __launch_bounds__(256) void vq_search_wide_kernel(const float* __restrict__ z, int ldz, const float* __restrict__ En, int K, int D,
                                                              int R, float* __restrict__ best_val, int* __restrict__ best_idx) {
     constexpr int T = FM_VQ_WIDE_TILE, KS = 32, LDT = KS + 1;          // row stride 33 floats: the 32 lanes of a half-wave hit 32 banks
@@ -228,18 +231,25 @@ __global__ __launch_bounds__(256) void vq_search_wide_kernel(const float* __rest
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ww = wave >> 1, wx = wave & 1;
     const int n0 = blockIdx.x * T, m0 = blockIdx.y * T;
-    // 1 / max(|z_r|, 1e-12) of the block's rows (F.normalize): a wave per row, float4 per lane
-    for (int r = wave; r < T; r += 4) {
-        const float* zr = z + (size_t)(m0 + r < R ? m0 + r : R - 1) * ldz;
-        float s = 0.f;
-        for (int d = lane * 4; d < D; d += 256) {
-            const float4 v = *(const float4*)(zr + d);
-            s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+    if constexpr (MEM) {
+        z += (size_t)blockIdx.z * D;
+        En += (size_t)blockIdx.z * K * D;
+        best_val += (size_t)blockIdx.z * R * gridDim.x;
+        best_idx += (size_t)blockIdx.z * R * gridDim.x;
+    } else {
+        // 1 / max(|z_r|, 1e-12) of the block's rows (F.normalize): a wave per row, float4 per lane
+        for (int r = wave; r < T; r += 4) {
+            const float* zr = z + (size_t)(m0 + r < R ? m0 + r : R - 1) * ldz;
+            float s = 0.f;
+            for (int d = lane * 4; d < D; d += 256) {
+                const float4 v = *(const float4*)(zr + d);
+                s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+            }
+            s = wave_sum(s);
+            if (lane == 0) inv[r] = 1.0f / fmaxf(sqrtf(s), 1e-12f);
         }
-        s = wave_sum(s);
-        if (lane == 0) inv[r] = 1.0f / fmaxf(sqrtf(s), 1e-12f);
+        __syncthreads();
     }
-    __syncthreads();
     f32x16_t acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -256,7 +266,7 @@ __global__ __launch_bounds__(256) void vq_search_wide_kernel(const float* __rest
         const int r = lr + 32 * p;
         ep[p] = En + (size_t)(n0 + r < K ? n0 + r : K - 1) * D + lc;
         zp[p] = z + (size_t)(m0 + r < R ? m0 + r : R - 1) * ldz + lc;
-        zi[p] = inv[r];
+        zi[p] = MEM ? 1.0f : inv[r];
     }
     float4 ereg[4], zreg[4];
     auto load = [&](int k0) {
@@ -272,7 +282,8 @@ __global__ __launch_bounds__(256) void vq_search_wide_kernel(const float* __rest
         for (int p = 0; p < 4; ++p) {
             float* ed = Es + (lr + 32 * p) * LDT + lc; float* zd = Zs + (lr + 32 * p) * LDT + lc;
             ed[0] = ereg[p].x; ed[1] = ereg[p].y; ed[2] = ereg[p].z; ed[3] = ereg[p].w;
-            zd[0] = zreg[p].x * zi[p]; zd[1] = zreg[p].y * zi[p]; zd[2] = zreg[p].z * zi[p]; zd[3] = zreg[p].w * zi[p];
+            if constexpr (MEM) { zd[0] = zreg[p].x; zd[1] = zreg[p].y; zd[2] = zreg[p].z; zd[3] = zreg[p].w; }
+            else { zd[0] = zreg[p].x * zi[p]; zd[1] = zreg[p].y * zi[p]; zd[2] = zreg[p].z * zi[p]; zd[3] = zreg[p].w * zi[p]; }
         }
     };
     load(0);
@@ -322,6 +333,28 @@ __global__ __launch_bounds__(256) void vq_search_wide_kernel(const float* __rest
     }
 }
 
+// fm_memcodes_assign: the winner of (row r, head h = blockIdx.y) across the code tiles (ascending: the first maximum wins), the token in
+// head-major layout (B, H, G) and the head's slice of quant (B, H d, G) gathered from values (H, K, d)
+__global__ __launch_bounds__(256) void memcodes_merge_kernel(const float* __restrict__ best_val, const int* __restrict__ best_idx, int tiles,
+                                                             const float* __restrict__ values, long long* __restrict__ tokens,
+                                                             float* __restrict__ quant, int R, int d, int H, int K, int G) {
+    const int r = blockIdx.x * 256 + threadIdx.x, h = blockIdx.y;
+    if (r >= R) return;
+    const size_t w = ((size_t)h * R + r) * tiles;
+    float bv = best_val[w];
+    int bi = best_idx[w];
+    for (int s = 1; s < tiles; ++s) {
+        const float v = best_val[w + s];
+        if (v > bv) { bv = v; bi = best_idx[w + s]; }
+    }
+    const int b = r / G, g = r % G;
+    tokens[((size_t)b * H + h) * G + g] = bi;
+    if (quant) {
+        const float* src = values + ((size_t)h * K + bi) * d;
+        for (int c = 0; c < d; ++c) quant[(((size_t)b * H + h) * d + c) * G + g] = src[c];
+    }
+}
+
 }  // namespace
 
 extern "C" int fm_vq_assign_wide(const void* z, int ldz, const void* codes_normalized, const void* embed, int K, int D, int R,
@@ -333,11 +366,34 @@ extern "C" int fm_vq_assign_wide(const void* z, int ldz, const void* codes_norma
     const int tiles = (K + FM_VQ_WIDE_TILE - 1) / FM_VQ_WIDE_TILE;
     FM_CHECK_ARG(code_tiles == tiles, "fm_vq_assign_wide: code_tiles=%d, expected ceil(K / %d) = %d (the scratch row length)", code_tiles, FM_VQ_WIDE_TILE, tiles);
     FM_CHECK_ARG((R + FM_VQ_WIDE_TILE - 1) / FM_VQ_WIDE_TILE <= 65535, "fm_vq_assign_wide: too many rows (R=%d)", R);
-    hipLaunchKernelGGL(vq_search_wide_kernel, dim3(tiles, (R + FM_VQ_WIDE_TILE - 1) / FM_VQ_WIDE_TILE), dim3(256), 0, (hipStream_t)stream, (const float*)z, ldz,
+    hipLaunchKernelGGL(vq_search_wide_kernel<false>, dim3(tiles, (R + FM_VQ_WIDE_TILE - 1) / FM_VQ_WIDE_TILE), dim3(256), 0, (hipStream_t)stream, (const float*)z, ldz,
                        (const float*)codes_normalized, K, D, R, (float*)ws_val, (int*)ws_idx);
     hipLaunchKernelGGL(vq_merge_kernel, dim3((R + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)ws_val, (const int*)ws_idx, tiles,
                        (const float*)embed, (long long*)tokens, (float*)quant, R, D, tokens_per_image);
     FM_CHECK_LAUNCH("fm_vq_assign_wide");
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Memcodes (quantize_memcodes.py:84-101, eval branch): H heads, each an arg-max of plain inner products <z[r, h d : (h + 1) d], keys[h][j]>
+// over the head's K keys, out = values[h][token].  The same 128 x 128 exact-fp32 MFMA tile as above with the head on blockIdx.z and the row
+// normalisation compiled out.  Upstream multiplies the query by d^-0.5 first; a positive scale cannot change an arg-max, so it is left out.
+// ------------------------------------------------------------------------------------------------
+extern "C" int fm_memcodes_assign(const void* z, int ldz, const void* keys, const void* values, int K, int d, int H, int R,
+                                  int tokens_per_image, void* ws_val, void* ws_idx, int code_tiles, int64_t* tokens, void* quant, void* stream) {
+    FM_CHECK_ARG(z && keys && values && ws_val && ws_idx && tokens, "fm_memcodes_assign: null pointer");
+    FM_CHECK_ARG(d % 4 == 0 && d >= 8 && d <= 4096, "fm_memcodes_assign: head width d=%d unsupported (a multiple of 4 in [8, 4096])", d);
+    FM_CHECK_ARG(H >= 1 && K >= 1 && R >= 1 && tokens_per_image >= 1, "fm_memcodes_assign: bad shape (H, K, R, tokens_per_image >= 1)");
+    FM_CHECK_ARG(ldz % 4 == 0 && (long long)ldz >= (long long)H * d, "fm_memcodes_assign: bad row stride ldz=%d (ldz %% 4 == 0, ldz >= H d = %lld)", ldz, (long long)H * d);
+    FM_CHECK_ARG(((((uintptr_t)z | (uintptr_t)keys)) & 15) == 0, "fm_memcodes_assign: z and keys must be 16-byte aligned");
+    const int tiles = (K + FM_VQ_WIDE_TILE - 1) / FM_VQ_WIDE_TILE, row_tiles = (R + FM_VQ_WIDE_TILE - 1) / FM_VQ_WIDE_TILE;
+    FM_CHECK_ARG(code_tiles == tiles, "fm_memcodes_assign: code_tiles=%d, expected ceil(K / %d) = %d (the scratch row length)", code_tiles, FM_VQ_WIDE_TILE, tiles);
+    FM_CHECK_ARG(row_tiles <= 65535 && H <= 65535, "fm_memcodes_assign: grid too large (R=%d, H=%d: at most 65535 row tiles and heads)", R, H);
+    hipLaunchKernelGGL(vq_search_wide_kernel<true>, dim3(tiles, row_tiles, H), dim3(256), 0, (hipStream_t)stream, (const float*)z, ldz, (const float*)keys, K, d, R,
+                       (float*)ws_val, (int*)ws_idx);
+    hipLaunchKernelGGL(memcodes_merge_kernel, dim3((R + 255) / 256, H), dim3(256), 0, (hipStream_t)stream, (const float*)ws_val, (const int*)ws_idx, tiles,
+                       (const float*)values, (long long*)tokens, (float*)quant, R, d, H, K, tokens_per_image);
+    FM_CHECK_LAUNCH("fm_memcodes_assign");
     return 0;
 }
 

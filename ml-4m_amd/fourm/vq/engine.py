@@ -264,6 +264,8 @@ def _batch_invariant(vq):
 
 @torch.no_grad()
 def vq_encode(vq, x):
+    if vq._is_mlp():
+        return _mlp_vq_encode(vq, x)
     _check_search(vq)
     with _batch_invariant(vq):
         return _vq_encode(vq, x)
@@ -348,6 +350,8 @@ def _decode_rows_impl(vq, q_rows, B, nh, nw, st):
 def vqvae_decode_quant(vq, quant):
     """(B, latent_dim, h, w) -> (B, C, H, W)   [vqvae.py:454-465]"""
     B, Ld, nh, nw = quant.shape
+    if vq._is_mlp():
+        return _mlp_decode_quant(vq, quant)
     rows = quant.detach().float().permute(0, 2, 3, 1).reshape(B * nh * nw, Ld).contiguous()
     return _decode_rows(vq, rows, B, nh, nw)
 
@@ -356,6 +360,182 @@ def vqvae_decode_quant(vq, quant):
 def vqvae_decode_tokens(vq, tokens):
     B, nh, nw = tokens.shape
     return _decode_rows(vq, _quant_rows(vq, tokens, tokens.device), B, nh, nw)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# MLP tokenizers with the Memcodes quantizer (human poses, DINOv2 / ImageBind global features), inference
+#   upstream: VQ.encode / VQVAE.decode_quant (vq/vqvae.py:302-318, :454-465), BottleneckMLP / StandardMLP.forward (vq/models/mlp_models.py:52-72,
+#             :95-115), Memcodes.forward eval branch (vq/quantizers/quantize_memcodes.py:70-124)
+# Everything is point-wise over the rows (B h w, C) and exact fp32 (the tokenization script runs these models without autocast): fm_gemm_f32
+# (bias, GELU and residual epilogues), fm_layernorm_fwd, fm_memcodes_assign.  fm_gemm_f32 picks its kernel from strides and alignment, never
+# from the number of rows, and every operand row is staged in a buffer of this engine (same alignment whatever tensor the caller sliced):
+# a sample's tokens, quant and reconstruction are the same bits in any batch.
+# ---------------------------------------------------------------------------------------------------------------------------------
+class _MlpEngine:
+    """Scratch and cached operands of one MLP encoder / decoder / Memcodes quantizer on its device."""
+
+    def __init__(self, device):
+        self.device = device
+        self.ws = Workspace(device, per_stream=True)
+        self._cache = {}
+
+
+def _mlp_engine(mod, probe) -> _MlpEngine:
+    eng = getattr(mod, "_hip_engine", None)
+    dev = probe.device
+    if eng is None or eng.device != dev:
+        if dev.type != "cuda":
+            raise RuntimeError("the tokenizer computes on an MI355X through libfourm_hip.so; move it to the GPU first")
+        eng = _MlpEngine(dev)
+        object.__setattr__(mod, "_hip_engine", eng)
+    return eng
+
+
+def _check_mlp(mlp):
+    """Refuse widths fm_layernorm_fwd cannot serve BEFORE anything is launched."""
+    for ln in mlp.layernorms:
+        D = ln.normalized_shape[0]
+        if D % 4 or D > 2048 or ln.weight is None or ln.bias is None:
+            raise NotImplementedError(f"MLP tokenizer width {D}: fm_layernorm_fwd is built for affine norms over a multiple of 4 up to 2048 features")
+
+
+def _check_memcodes(q):
+    d = q.dim // q.heads
+    if d % 4 or d < 8 or d > 4096:
+        raise NotImplementedError(f"Memcodes with {q.heads} heads over dim={q.dim} (head width {d}): fm_memcodes_assign is built for head widths that are "
+                                  "a multiple of 4 in [8, 4096]")
+
+
+def _stage_rows(eng, name, x):
+    """(B, C, h, w) -> rows (B h w, C) f32 in a buffer of the engine ('b d h w -> (b h w) d')."""
+    B, C, h, w = x.shape
+    rows = eng.ws.get(name, (B * h * w, C), torch.float32)
+    rows.view(B, h, w, C).copy_(x.detach().permute(0, 2, 3, 1))
+    return rows
+
+
+def _mlp_rows(eng, mlp, x, R, prefix):
+    """BottleneckMLP / StandardMLP on rows x (R, dim_in) f32 -> (R, dim_out) f32 (a buffer of the engine)."""
+    from .models.mlp_models import BottleneckMLP
+    ws, f32 = eng.ws, torch.float32
+    lin = mlp.linear_in
+    h = ws.get(prefix + ".h0", (R, lin.out_features), f32)
+    ops.gemm_nt(x, lin.weight.detach(), h, epilogue=L.EPI_F32, bias=lin.bias, M=R, N=lin.out_features, K=lin.in_features)
+    if isinstance(mlp, BottleneckMLP):
+        for i, (blk, ln) in enumerate(zip(mlp.blocks, mlp.layernorms)):          # x = x + fc2(GELU(fc1(LayerNorm(x))))
+            fc1, fc2 = blk.block[0], blk.block[2]
+            n = ws.get(prefix + ".n", tuple(h.shape), f32)
+            ops.layernorm_fwd(h, ln.weight, ln.bias, n, eps=ln.eps, R=R)
+            t = ws.get(prefix + ".t", (R, fc1.out_features), f32)
+            ops.gemm_nt(n, fc1.weight.detach(), t, epilogue=L.EPI_GELU, bias=fc1.bias, M=R, N=fc1.out_features, K=fc1.in_features)
+            nxt = ws.get(f"{prefix}.h{(i + 1) % 2}", (R, fc2.out_features), f32)
+            ops.gemm_nt(t, fc2.weight.detach(), nxt, epilogue=L.EPI_RESIDUAL, res=h, bias=fc2.bias, M=R, N=fc2.out_features, K=fc2.in_features)
+            h = nxt
+    else:
+        for i, (layer, ln) in enumerate(zip(mlp.layers, mlp.layernorms)):       # z = layer(LayerNorm(z)), no activation
+            n = ws.get(prefix + ".n", tuple(h.shape), f32)
+            ops.layernorm_fwd(h, ln.weight, ln.bias, n, eps=ln.eps, R=R)
+            h = ws.get(f"{prefix}.h{(i + 1) % 2}", (R, layer.out_features), f32)
+            ops.gemm_nt(n, layer.weight.detach(), h, epilogue=L.EPI_F32, bias=layer.bias, M=R, N=layer.out_features, K=layer.in_features)
+    lo = mlp.linear_out
+    out = ws.get(prefix + ".out", (R, lo.out_features), f32)
+    ops.gemm_nt(h, lo.weight.detach(), out, epilogue=L.EPI_F32, bias=lo.bias, M=R, N=lo.out_features, K=lo.in_features)
+    return out
+
+
+def memcodes_tables(q):
+    """(keys, values), each (H, K, d) f32: codes[h] @ to_k.weight[h] and codes[h] @ to_v.weight[h] by the fp32 GEMM, one launch per head and
+    table, cached on the quantizer's engine until a parameter changes (the stamp carries the weight epoch read at call time: FusedAdamW writes
+    parameters without moving ``_version``)."""
+    eng = _mlp_engine(q, q.codes)
+    params = (q.codes, q.to_k.weight, q.to_v.weight)
+    stamp = tuple((p._version, p.data_ptr()) for p in params) + (hip_engine._WEIGHT_EPOCH,)
+    hit = eng._cache.get("memcodes")
+    if hit is None or hit[0] != stamp:
+        H, K, d = q.codes.shape
+        codes = q.codes.detach().contiguous()
+        tables = []
+        for w in (q.to_k.weight, q.to_v.weight):
+            wt = w.detach().transpose(1, 2).contiguous()                         # (H, c, d): the NT operand of out[n][c] = sum_d codes[n][d] w[d][c]
+            out = torch.empty(H, K, d, dtype=torch.float32, device=codes.device)
+            for h in range(H):
+                ops.gemm_nt(codes[h], wt[h], out[h], epilogue=L.EPI_F32, M=K, N=d, K=d)
+            tables.append(out)
+        torch.cuda.current_stream(codes.device).synchronize()                    # (built once: complete before another stream may pick it up)
+        hit = eng._cache["memcodes"] = (stamp, tables[0], tables[1])
+    return hit[1], hit[2]
+
+
+def _memcodes_assign(q, z, B, nh, nw):
+    """Latent rows z (B nh nw, >= dim) f32 -> tokens (B, H, nh, nw) int64 ((B, nh, nw) with one head), quant (B, dim, nh, nw) f32."""
+    eng = _mlp_engine(q, q.codes)
+    H, K, d = q.codes.shape
+    G, R = nh * nw, B * nh * nw
+    keys, values = memcodes_tables(q)
+    tiles = -(-K // L.VQ_WIDE_TILE)
+    wv = eng.ws.get("memcodes.wv", (H, R, tiles), torch.float32)
+    wi = eng.ws.get("memcodes.wi", (H, R, tiles), torch.int32)
+    tokens = torch.empty((B, H, nh, nw) if H > 1 else (B, nh, nw), dtype=torch.int64, device=z.device)
+    quant = torch.empty(B, H * d, nh, nw, dtype=torch.float32, device=z.device)
+    # 128 rows x 128 keys tiles of exact-fp32 MFMA per head, reduced to (best score, lowest index) per tile: no (R, K) matrix
+    L.check(L.memcodes_assign(ops._p(z), z.stride(0), ops._p(keys), ops._p(values), K, d, H, R, G, ops._p(wv), ops._p(wi), tiles, ops._p(tokens),
+                              ops._p(quant), ops._stream()))
+    return tokens, quant
+
+
+def memcodes_forward(q, x):
+    """Memcodes.forward in eval mode on (B, dim, h, w): (out, zeros(1), tokens)."""
+    _check_memcodes(q)
+    B, C, nh, nw = x.shape
+    assert C == q.dim, f"Memcodes(dim={q.dim}) got {C} channels"
+    z = _stage_rows(_mlp_engine(q, q.codes), "memcodes.z", x)
+    tokens, quant = _memcodes_assign(q, z, B, nh, nw)
+    return quant, torch.zeros(1, device=z.device), tokens
+
+
+def memcodes_embedding(q, tokens):
+    """tokens (B, H, 1, 1) -> values[h][token] with the heads concatenated, (B, H d, 1, 1): rows of the cached value table."""
+    H, K, d = q.codes.shape
+    _, values = memcodes_tables(q)
+    B = tokens.shape[0]
+    idx = (tokens.reshape(B, H).to(values.device) + torch.arange(H, device=values.device) * K).reshape(-1).contiguous()
+    out = torch.empty(B, H * d, 1, 1, dtype=torch.float32, device=values.device)
+    L.check(L.embed_rows_f32(ops._p(values), ops._p(idx), ops._p(out), d, B * H, d, ops._stream()))
+    return out
+
+
+def _mlp_vq_encode(vq, x):
+    """(B, C, h, w) -> (quant (B, latent_dim, h, w), zeros(1), tokens (B, heads, h, w)): linear_in, the blocks, linear_out, quant_proj, code search."""
+    enc, q = vq.encoder, vq.quantize
+    _check_mlp(enc)
+    _check_memcodes(q)
+    eng = _mlp_engine(enc, enc.linear_in.weight)
+    B, C, nh, nw = x.shape
+    assert C == enc.dim_in, f"the encoder takes {enc.dim_in} channels, got {C}"
+    R, Ld = B * nh * nw, vq.latent_dim
+    feat = _mlp_rows(eng, enc, _stage_rows(eng, "enc.x", x), R, "enc")
+    z = eng.ws.get("enc.z", (R, Ld), torch.float32)
+    ops.gemm_nt(feat, vq.quant_proj.weight.detach().reshape(Ld, vq.enc_dim), z, epilogue=L.EPI_F32, bias=vq.quant_proj.bias, M=R, N=Ld, K=vq.enc_dim)
+    tokens, quant = _memcodes_assign(q, z, B, nh, nw)
+    vq._last_latents = z.view(B, nh * nw, Ld)
+    return quant, torch.zeros(1, device=z.device), tokens
+
+
+def _mlp_decode_quant(vq, quant):
+    """(B, latent_dim, h, w) -> (B, C, h, w): post_quant_proj, the MLP decoder, 'b (h w) d -> b d h w'."""
+    dec = vq.decoder
+    _check_mlp(dec)
+    eng = _mlp_engine(dec, dec.linear_in.weight)
+    B, Ld, nh, nw = quant.shape
+    R = B * nh * nw
+    pq = vq.post_quant_proj
+    s = eng.ws.get("dec.s", (R, vq.dec_dim), torch.float32)
+    ops.gemm_nt(_stage_rows(eng, "dec.q", quant), pq.weight.detach().reshape(vq.dec_dim, Ld), s, epilogue=L.EPI_F32, bias=pq.bias, M=R, N=vq.dec_dim, K=Ld)
+    out = _mlp_rows(eng, dec, s, R, "dec")
+    C = dec.dim_out
+    img = torch.empty(B, C, nh, nw, dtype=torch.float32, device=out.device)
+    img.copy_(out.view(B, nh, nw, C).permute(0, 3, 1, 2))
+    return img
 
 
 def _post_mlp_bwd(eng, vit, sp, g, g_bf, R):

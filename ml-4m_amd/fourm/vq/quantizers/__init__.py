@@ -1,4 +1,5 @@
 from .quantize_lucid import VectorQuantize as VectorQuantizerLucid
+from .quantize_memcodes import Memcodes
 
 from fourm import _upstream as _up
 

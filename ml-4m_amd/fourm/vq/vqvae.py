@@ -17,7 +17,8 @@ import torch
 import torch.nn as nn
 
 from .models import vit_models
-from .quantizers import VectorQuantizerLucid
+from .models.mlp_models import build_mlp
+from .quantizers import Memcodes, VectorQuantizerLucid
 
 try:
     from huggingface_hub import PyTorchModelHubMixin
@@ -41,10 +42,18 @@ class VQ(nn.Module, PyTorchModelHubMixin):
         super().__init__()
         if undo_std and (n_channels != 3 or n_labels is not None):
             raise ValueError("undo_std expects ImageNet-standardised RGB input")
-        if quant_type != "lucid":
+        if quant_type not in ("lucid", "memcodes"):
             raise NotImplementedError(f"quant_type {quant_type!r} has no HIP kernel")
-        if "vit" not in enc_type or not hasattr(vit_models, enc_type):
+        mlp_enc = "vit" not in enc_type and "MLP" in enc_type            # (upstream's order: 'vit' first, then 'MLP', vqvae.py:149-159)
+        if not mlp_enc and ("vit" not in enc_type or not hasattr(vit_models, enc_type)):
             raise NotImplementedError(f"{enc_type} not implemented.")
+        if mlp_enc != (quant_type == "memcodes"):
+            # no upstream configuration pairs them: the MLP path ends in fm_memcodes_assign, the ViT path in the cosine / Euclidean searches
+            raise NotImplementedError(f"enc_type {enc_type!r} with quant_type {quant_type!r}: the MLP encoders are built with the memcodes quantizer "
+                                      "and the ViT encoders with the lucid quantizer only")
+        if mlp_enc and (n_labels is not None or undo_std):
+            raise NotImplementedError(f"n_labels / undo_std with the MLP encoder {enc_type!r}: class maps and ImageNet-standardised pixels are inputs "
+                                      "of the ViT tokenizers (they are folded into the patch gather)")
         for k, v in dict(image_size=image_size, n_channels=n_channels, n_labels=n_labels, enc_type=enc_type, patch_proj=patch_proj,
                          post_mlp=post_mlp, patch_size=patch_size, quant_type=quant_type, codebook_size=codebook_size,
                          num_codebooks=num_codebooks, latent_dim=latent_dim, norm_codes=norm_codes, norm_latents=norm_latents,
@@ -56,11 +65,15 @@ class VQ(nn.Module, PyTorchModelHubMixin):
         self.cls_emb = nn.Embedding(num_embeddings=n_labels, embedding_dim=n_channels) if n_labels is not None else None
         if n_labels is not None:
             self.colorize = torch.randn(3, n_labels, 1, 1)
-        self.encoder = getattr(vit_models, enc_type)(in_channels=n_channels, patch_size=patch_size, resolution=image_size_enc or image_size,
-                                                     patch_proj=patch_proj, post_mlp=post_mlp)
-        self.enc_dim = self.encoder.dim_tokens
+        if mlp_enc:          # one vector per position, point-wise MLP (vqvae.py:155-157)
+            self.encoder = build_mlp(model_id=enc_type, dim_in=n_channels, dim_out=None)
+            self.enc_dim = self.encoder.dim_out
+        else:
+            self.encoder = getattr(vit_models, enc_type)(in_channels=n_channels, patch_size=patch_size, resolution=image_size_enc or image_size,
+                                                         patch_proj=patch_proj, post_mlp=post_mlp)
+            self.enc_dim = self.encoder.dim_tokens
         self.quant_proj = torch.nn.Conv2d(self.enc_dim, self.latent_dim, 1)
-        self.quantize = VectorQuantizerLucid(dim=latent_dim, codebook_size=codebook_size, codebook_dim=latent_dim, heads=num_codebooks,
+        self.quantize = Memcodes(dim=latent_dim, codebook_size=codebook_size, heads=num_codebooks, temperature=1.) if mlp_enc else VectorQuantizerLucid(dim=latent_dim, codebook_size=codebook_size, codebook_dim=latent_dim, heads=num_codebooks,
                                              use_cosine_sim=norm_codes, threshold_ema_dead_code=threshold_ema_dead_code,
                                              code_replacement_policy=code_replacement_policy, sync_codebook=sync_codebook, decay=ema_decay,
                                              commitment_weight=commitment_weight, norm_latents=norm_latents, kmeans_init=kmeans_init)
@@ -113,12 +126,18 @@ class VQ(nn.Module, PyTorchModelHubMixin):
 
     def _inference_only(self):
         """Why this configuration cannot train here (None: it can).  Checked in Python before any kernel is launched."""
+        if self._is_mlp():
+            return (f"the MLP tokenizers ({self.enc_type} with the memcodes quantizer) are inference only: the straight-through gumbel-softmax "
+                    "forward of Memcodes and the backward of the MLP path are not built")
         if self.latent_dim > 64:
             return (f"latent_dim={self.latent_dim} is inference only: the codebook statistics, EMA update and latent gradient kernels "
                     "(fm_vq_code_stats, fm_vq_ema_update, fm_vq_latent_grad*) are built for latent_dim <= 64")
         if hasattr(getattr(self, "decoder", None), "out_conv"):
             return "a decoder with out_conv=True is inference only: the ConvNeXt blocks (fm_convnext_block) have no backward kernel"
         return None
+
+    def _is_mlp(self):
+        return isinstance(self.quantize, Memcodes)
 
     def _encode(self, x):
         from .engine import vq_encode
@@ -159,13 +178,21 @@ class VQVAE(VQ):
         kwargs["ckpt_path"] = None
         super().__init__(*args, **kwargs)
         self.ckpt_path = ckpt_path
-        if "vit" not in dec_type or not hasattr(vit_models, dec_type):
+        mlp_dec = "vit" not in dec_type and "MLP" in dec_type
+        if not mlp_dec and ("vit" not in dec_type or not hasattr(vit_models, dec_type)):
             raise NotImplementedError(f"{dec_type} not implemented.")
+        if mlp_dec != self._is_mlp():
+            raise NotImplementedError(f"enc_type {self.enc_type!r} with dec_type {dec_type!r}: a ViT / MLP mix across encoder and decoder is not built "
+                                      "(no upstream configuration uses one)")
         self.dec_type, self.out_conv = dec_type, out_conv
-        self.decoder = getattr(vit_models, dec_type)(out_channels=self.n_channels if self.n_labels is None else self.n_labels, patch_size=patch_size_dec or self.patch_size,
-                                                     resolution=image_size_dec or self.image_size, out_conv=out_conv, post_mlp=self.post_mlp,
-                                                     patch_proj=self.patch_proj)
-        self.dec_dim = self.decoder.dim_tokens
+        if mlp_dec:          # (vqvae.py:441-443)
+            self.decoder = build_mlp(model_id=dec_type, dim_in=None, dim_out=self.n_channels)
+            self.dec_dim = self.decoder.dim_in
+        else:
+            self.decoder = getattr(vit_models, dec_type)(out_channels=self.n_channels if self.n_labels is None else self.n_labels, patch_size=patch_size_dec or self.patch_size,
+                                                         resolution=image_size_dec or self.image_size, out_conv=out_conv, post_mlp=self.post_mlp,
+                                                         patch_proj=self.patch_proj)
+            self.dec_dim = self.decoder.dim_tokens
         self.post_quant_proj = torch.nn.Conv2d(self.latent_dim, self.dec_dim, 1)
         if self.ckpt_path is not None:
             self.init_from_ckpt(self.ckpt_path, ignore_keys=self.ignore_keys)
@@ -178,6 +205,8 @@ class VQVAE(VQ):
     @torch.no_grad()
     def decode_tokens(self, tokens: torch.LongTensor, **kwargs) -> torch.Tensor:
         from .engine import vqvae_decode_tokens
+        if self._is_mlp():       # tokens (B, heads, 1, 1): upstream's decode_quant(tokens_to_embedding(tokens))
+            return self.decode_quant(self.tokens_to_embedding(tokens))
         return vqvae_decode_tokens(self, tokens)
 
     def forward(self, x: torch.Tensor, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -197,7 +226,9 @@ class VQVAE(VQ):
         return dec, code_loss
 
     def _eval_forward(self, x):
-        _, code_loss, tokens = self.encode(x)
+        quant, code_loss, tokens = self.encode(x)
+        if self._is_mlp():       # as upstream, from quant (vqvae.py:478-481): any grid; on 1 x 1 the same bits as decode_tokens(tokens)
+            return self.decode_quant(quant), code_loss
         return self.decode_tokens(tokens), code_loss
 
     def autoencode(self, x: torch.Tensor, **kwargs) -> torch.Tensor:
