@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define FM_ABI_VERSION 10
+#define FM_ABI_VERSION 11
 int fm_abi_version(void);
 const char* fm_last_error(void);
 
@@ -347,6 +347,25 @@ int fm_add_bf16_f32(const void* x, const void* delta, void* out, int64_t n, void
  * row stride ld (scale f32 per sample = mask / keep_prob).  The forward scales a residual branch's output, the backward the bf16
  * gradient copy that enters the branch.  N, ld multiples of 8. */
 int fm_scale_rows_bf16(void* x, int ld, const void* scale, int rows_per_sample, int R, int N, void* stream);
+
+/* Low-rank adapters (LoRAWrapper, fourm/models/lora_utils.py:44-81: y = linear(x) + scale * lora_up(lora_down(x))), csrc/lora.hip.
+ * P = x down^T (fp32 accumulation over K), y += scale * P up^T in place (fp32 sum, rounded once to y's type), P written to p_out.
+ * x: (R, K) row stride ldx; y: (R, N) row stride ldy; x_f32 / y_f32 select fp32 instead of bf16 elements (bf16 x with fp32 y is
+ * built, fp32 x with bf16 y is not).  down, up: fp32, addressed through element strides: down(j, k) = down[j * down_sr + k * down_sk],
+ * up(n, j) = up[n * up_sn + j * up_sr] - an nn.Linear pair passes (K, 1) and (r, 1).  The backward's dX += scale * (dY up) down is the
+ * same call with the roles exchanged: x = dY, "down" = up read as (1, r), "up" = down read as (1, K), y = dX, and p_out receives
+ * Q = dY up.  p_out: f32 (R, r) contiguous.  Rows >= R and columns >= K / N of x and y are neither read as values nor written.
+ * Refused (-1): null pointers, r < 1 or r > 64, R, K, N < 1, ldx / ldy not a multiple of 4 or smaller than K / N, x / y not aligned
+ * to 4 elements. */
+int fm_lora_apply(const void* x, int ldx, const void* down, int64_t down_sr, int64_t down_sk, const void* up, int64_t up_sn, int64_t up_sr,
+                  void* y, int ldy, float scale, void* p_out, int R, int K, int N, int r, int x_f32, int y_f32, void* stream);
+/* out(c, j) (+)= scale * sum_{row < R} a[row][c] * b[row][j], out(c, j) = out[c * out_sn + j * out_sr] fp32: the adapters' gradients.
+ * a: (R, n) bf16 (fp32 with a_f32) of row stride lda; b: f32 (R, r) contiguous.  d(lora_up) = scale dY^T P is (a, b) = (dY, P) with
+ * strides (r, 1); d(lora_down) = scale Q^T x is (a, b) = (x, Q) with strides (1, K).  accumulate == 0 overwrites.  Rows >= R are
+ * never read.  The row ranges of different workgroups meet in fp32 atomics: the sum order, and so the last bits, vary from run to run.
+ * Refused (-1): null pointers, r < 1 or r > 64, R, n < 1, lda not a multiple of 4 or smaller than n, a not aligned to 4 elements. */
+int fm_lora_grad(const void* a, int lda, const void* b, void* out, int64_t out_sn, int64_t out_sr, float scale, int accumulate,
+                 int R, int n, int r, int a_f32, void* stream);
 
 /* torch.optim.AdamW update on a contiguous fp32 range (fourm/utils/optim_factory.py:239-240);
  * grad_mult: optional device scalar multiplied into the gradient (clipping).

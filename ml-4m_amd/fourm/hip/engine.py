@@ -62,6 +62,32 @@ def ru(x, m):
     return (x + m - 1) // m * m
 
 
+def is_lora(lin) -> bool:
+    """A Linear wrapped by fourm.models.lora_utils.LoRAWrapper (``weight`` / ``bias`` then read the base Linear's)."""
+    return hasattr(lin, "lora_down")
+
+
+def check_lora_targets(model):
+    """LoRA wrappers are run where the engine adds the low-rank term behind the base GEMM: the attention Linears of the trunk blocks.
+    Anywhere else (MLP, embeddings, to_logits, context projection) the wrapped Linear would silently compute without its adapter."""
+    from fourm.models.lora_utils import MAX_LORA_WIDTH, LoRAWrapper
+    ok = set()
+    for blk in model.encoder:
+        ok |= {id(blk.attn.qkv), id(blk.attn.proj)}
+    for blk in model.decoder:
+        ok |= {id(blk.self_attn.qkv), id(blk.self_attn.proj), id(blk.cross_attn.q), id(blk.cross_attn.kv), id(blk.cross_attn.proj)}
+    for name, mod in model.named_modules():
+        if not isinstance(mod, LoRAWrapper):
+            continue
+        if id(mod) not in ok:
+            raise NotImplementedError(f"LoRA wrapper at '{name}': the HIP engine adapts the attention Linears of the encoder / decoder blocks only "
+                                      "(the MLP's fc1 / fc3 run as one launch whose SwiGLU epilogue consumes the pre-activation; embeddings and "
+                                      "heads have no low-rank path)")
+        width = mod.lora_down.weight.shape[0]
+        if width > MAX_LORA_WIDTH:
+            raise NotImplementedError(f"LoRA wrapper at '{name}': rank x packed Linears = {width} exceeds {MAX_LORA_WIDTH}")
+
+
 class Shadow:
     """One bf16 weight shadow: ``buf`` plus the jobs (fp32 master view -> bf16 view, transpose) that fill it and
     the stamp of the masters it was last built from."""
@@ -154,6 +180,7 @@ class FourMEngine:
     def __init__(self, model):
         from fourm.models.fm_utils import GatedMlp, NormAttention, act_name
         self.model = model
+        check_lora_targets(model)
         self.D = model.dim
         blk = model.encoder[0] if len(model.encoder) else model.decoder[0]
         attn0 = blk.attn if hasattr(blk, "attn") else blk.self_attn
@@ -428,13 +455,15 @@ class FourMEngine:
     @property
     def hoist_ctx(self):
         """The context-norm hoist applies: every decoder block's context_norm is bias-free and its K/V projection has no bias (all 4M
-        swiglu_nobias configurations).  Decided once per engine (it fixes the order of the flat parameter store); which of the two tensors
+        swiglu_nobias configurations), and none is wrapped by a LoRA adapter (the fold keeps gamma in ONE all-layer kv weight image, which has no place
+        for a per-layer low-rank term).  Decided once per engine (it fixes the order of the flat parameter store); which of the two tensors
         are trainable is read at every backward."""
         h = getattr(self, "_hoist_ctx", None)
         if h is None:
             m = self.model
             h = HOIST_CTX and len(m.decoder) > 0 and all(
-                not isinstance(b.context_norm.bias, nn.Parameter) and b.cross_attn.kv.bias is None for b in m.decoder)
+                not isinstance(b.context_norm.bias, nn.Parameter) and b.cross_attn.kv.bias is None and not is_lora(b.cross_attn.kv)
+                for b in m.decoder)
             self._hoist_ctx = h
         return h
 
@@ -554,7 +583,30 @@ class FourMEngine:
         ops.layernorm_fwd(x, norm.weight, norm.bias, y, mean, rstd, row_map=row_map, eps=norm.eps, R=R)
         return y
 
-    def _residual(self, a, lin, x_res, x_out, R, N, K, defer):
+    def _lora_fwd(self, lin, x, y, R, sv=None, tag="", key=""):
+        """The low-rank branch of a wrapped Linear, added in place to the output ``y`` of its base GEMM: y += scale (x down^T) up^T.
+        P = x down^T (fp32, r columns) stays in the saved state for the adapters' gradients.  Plain Linears: nothing to do."""
+        if not is_lora(lin):
+            return
+        down, up = lin.lora_down.weight, lin.lora_up.weight
+        P = self._buf(sv, tag, "lora." + key, (x.shape[0], down.shape[0]), torch.float32)
+        ops.lora_apply(x, down, up, y, lin.scale, P, R, lin.in_features, lin.out_features)
+
+    def _lora_bwd(self, lin, dy, x, dx, P, R):
+        """Backward of the low-rank branch, issued AFTER the base dX GEMM of the same Linear has written ``dx``:
+        Q = dy up and dx += scale Q down in one launch, then d(up) += scale dy^T P and d(down) += scale Q^T x.  ``dy`` and ``x`` are the
+        operands the (possibly queued) base dW reads too - they are only read here."""
+        if not is_lora(lin):
+            return
+        down, up = lin.lora_down.weight, lin.lora_up.weight
+        Q = self.ws.get("bwd.lora_q", (dy.shape[0], down.shape[0]), torch.float32)
+        ops.lora_apply(dy, down, up, dx, lin.scale, Q, R, lin.out_features, lin.in_features, backward=True)
+        if up.requires_grad:
+            ops.lora_grad(dy, P, self.grad_view(up), lin.scale, R, lin.out_features)
+        if down.requires_grad:
+            ops.lora_grad(x, Q, self.grad_view(down), lin.scale, R, lin.in_features, transposed=True)
+
+    def _residual(self, a, lin, x_res, x_out, R, N, K, defer, sv=None, tag="", key="proj"):
         """x_out = x_res + a W^T (+ bias): fused in the GEMM epilogue, or (defer) a bf16 GEMM whose sum is owed to the next _ln(x_out).
         With stochastic depth active (self._drop_now = (per-sample scale, rows per sample)) the branch output is scaled first."""
         drop = self._drop_now
@@ -564,6 +616,7 @@ class FourMEngine:
             self._settle()
             delta = self.ws.get("fwd.delta", (x_out.shape[0], N), self.adt)
             ops.gemm_nt(a, self.w(lin.weight), delta, bias=lin.bias, M=R, N=N, K=K)
+            self._lora_fwd(lin, a, delta, R, sv, tag, key)
             if drop is not None:
                 ops.scale_rows_bf16(delta, drop[0], drop[1], R, N)
             self._pending = (x_out, x_res, delta, R)
@@ -571,6 +624,7 @@ class FourMEngine:
                 self._settle()
         else:
             ops.gemm_nt(a, self.w(lin.weight), x_out, epilogue=L.EPI_RESIDUAL, res=x_res, bias=lin.bias, M=R, N=N, K=K)
+            self._lora_fwd(lin, a, x_out, R, sv, tag, key)
 
     def _drop_scales(self, blk, B, n, sv, dp):
         """Per-branch DropPath scales of one block: ``dp`` when given (checkpoint recompute), freshly drawn in training mode, else None."""
@@ -644,6 +698,7 @@ class FourMEngine:
         qkv = self._buf(sv, tag, "qkv", (Rp, 3 * D), bf)
         o = self._buf(sv, tag, "o", (Rp, D), bf)
         ops.gemm_nt(h, self.w(attn.qkv.weight), qkv, bias=attn.qkv.bias, M=R, N=3 * D, K=D)
+        self._lora_fwd(attn.qkv, h, qkv, R, sv, tag, "qkv")
         q_in, k_in = qkv[:, :D], qkv[:, D:2 * D]
         if self.qk_norm:
             q_in, k_in = self._qk_norm_fwd(attn, q_in, k_in, R, R, Rp, Rp, sv, tag, "qkn")
@@ -652,7 +707,7 @@ class FourMEngine:
             sm = self._buf(sv, tag, "sm", (B, self.H, N), torch.float32)
             sl = self._buf(sv, tag, "sl", (B, self.H, N), torch.float32)
         ops.attn_fwd(q_in, k_in, qkv[:, 2 * D:], o, B, self.H, N, N, self.scale, stat_m=sm, stat_l=sl, zero_attn=getattr(attn, "allow_zero_attn", False), **mask)
-        self._residual(o, attn.proj, x_res, x_out, R, D, D, defer=True)       # (every caller normalises x_out next)
+        self._residual(o, attn.proj, x_res, x_out, R, D, D, defer=True, sv=sv, tag=tag, key="proj")       # (every caller normalises x_out next)
 
     def _cross_attn_fwd(self, attn, hq, hc, x_res, x_out, B, M, N, Rq, Rqp, Rc, Rcp, mask, sv, tag, w_kv=None):
         bf, D = self.adt, self.D
@@ -660,7 +715,9 @@ class FourMEngine:
         kv = self._buf(sv, tag, "kv", (Rcp, 2 * D), bf)
         o = self._buf(sv, tag, "o2", (Rqp, D), bf)
         ops.gemm_nt(hq, self.w(attn.q.weight), q, bias=attn.q.bias, M=Rq, N=D, K=D)
+        self._lora_fwd(attn.q, hq, q, Rq, sv, tag, "q")
         ops.gemm_nt(hc, self.w(attn.kv.weight) if w_kv is None else w_kv, kv, bias=attn.kv.bias, M=Rc, N=2 * D, K=D)
+        self._lora_fwd(attn.kv, hc, kv, Rc, sv, tag, "kv")       # (a wrapped kv never meets w_kv: hoist_ctx is off then)
         sm = sl = None
         if sv is not None:
             sm = self._buf(sv, tag, "sm2", (B, self.H, M), torch.float32)
@@ -669,7 +726,7 @@ class FourMEngine:
         if self.qk_norm:
             q_in, k_in = self._qk_norm_fwd(attn, q_in, k_in, Rq, Rc, Rqp, Rcp, sv, tag, "xqkn")
         ops.attn_fwd(q_in, k_in, kv[:, D:], o, B, self.H, M, N, self.scale, stat_m=sm, stat_l=sl, zero_attn=getattr(attn, "allow_zero_attn", False), **mask)
-        self._residual(o, attn.proj, x_res, x_out, Rq, D, D, defer=True)
+        self._residual(o, attn.proj, x_res, x_out, Rq, D, D, defer=True, sv=sv, tag=tag, key="proj2")
 
     def encoder_block_fwd(self, blk, x_in, B, N, mask, sv, tag, defer_out=False, out_name=None, dp=None):
         """x_in (Rp, D) f32 -> new (Rp, D) f32 buffer.  [upstream Block.forward, fm_utils.py:331-334]
@@ -891,7 +948,8 @@ class FourMEngine:
     def _flush_dW(self):
         """All weight gradients queued by the current block backward in ONE launch (fm_gemm_tn_multi).  Their operands - the
         bf16 output gradients and the saved activations of this layer - must still hold what they held when queued: the block
-        backwards write each residual-stream gradient copy to its own buffer until this point."""
+        backwards write each residual-stream gradient copy to its own buffer until this point.  The low-rank launches of a wrapped
+        Linear (_lora_bwd) only READ those operands; what they write is the dX buffer behind its base GEMM and the adapters' gradients."""
         jobs, self._dw_jobs = self._dw_jobs, None
         ops.gemm_tn_multi(jobs)
 
@@ -945,6 +1003,7 @@ class FourMEngine:
         self._dW(g_bf, sv["o"], attn.proj, R64)
         do = ws.get("bwd.do", (Rp, D), bf)
         ops.gemm_nt(g_bf, self.wt(attn.proj.weight), do, M=R, N=D, K=D)
+        self._lora_bwd(attn.proj, g_bf, sv["o"], do, sv.get("lora.proj"), R)
         dqkv = ws.get("bwd.dqkv", (Rp, 3 * D), bf)
         qkv = sv["qkv"]
         if self.qk_norm:
@@ -958,6 +1017,7 @@ class FourMEngine:
         self._dW(dqkv, sv["h1"], attn.qkv, R64)
         dh = ws.get("bwd.dh", (Rp, D), bf)
         ops.gemm_nt(dqkv, self.wt(attn.qkv.weight), dh, M=R, N=D, K=3 * D)
+        self._lora_bwd(attn.qkv, dqkv, sv["h1"], dh, sv.get("lora.qkv"), R)
         return dh
 
     def encoder_block_bwd(self, blk, sv, g, g_bf, B, N, mask):
@@ -996,6 +1056,7 @@ class FourMEngine:
         self._dW(g_bf, sv["o2"], xa.proj, Rq)
         do = ws.get("bwd.do", (Rqp, D), bf)
         ops.gemm_nt(g_bf, self.wt(xa.proj.weight), do, M=Rq, N=D, K=D)
+        self._lora_bwd(xa.proj, g_bf, sv["o2"], do, sv.get("lora.proj2"), Rq)
         dq = ws.get("bwd.dq", (Rqp, D), bf)
         dkv = ws.get("bwd.dkv", (Rcp, 2 * D), bf) if hoist is None else hoist[0]
         kv = sv["kv"]
@@ -1011,6 +1072,7 @@ class FourMEngine:
         self._dW(dq, sv["hq"], xa.q, Rq)
         dhq = ws.get("bwd.dh", (Rqp, D), bf)
         ops.gemm_nt(dq, self.wt(xa.q.weight), dhq, M=Rq, N=D, K=D)
+        self._lora_bwd(xa.q, dq, sv["hq"], dhq, sv.get("lora.q"), Rq)
         g_bf = ws.get("bwd.dec.gbf2", tuple(g_in.shape), g_in.dtype)
         self._ln_bwd(blk.query_norm, dhq, sv["y1"], sv, "nq", g, g_bf, Rq, dres=g)
         if dp:
@@ -1019,6 +1081,7 @@ class FourMEngine:
             self._dW(dkv, sv["hc"], xa.kv, Rc)
             dhc = ws.get("bwd.dhc", (Rcp, D), bf)
             ops.gemm_nt(dkv, self.wt(xa.kv.weight), dhc, M=Rc, N=D, K=2 * D)
+            self._lora_bwd(xa.kv, dkv, sv["hc"], dhc, sv.get("lora.kv"), Rc)
             self._ln_bwd(blk.context_norm, dhc, ctx, sv, "nc", dctx, dctx_bf, Rc, dres=dctx)     # accumulates over layers
         elif xa.kv.weight.requires_grad or blk.context_norm.weight.requires_grad:
             self._dw_jobs.append((dkv, hoist[1], hoist[2], 2 * D, D, Rc))                       # dL/d(W diag(gamma)) = dkv^T x_hat

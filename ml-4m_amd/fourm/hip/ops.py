@@ -580,3 +580,43 @@ def dense_decoder_mask(cs, mod, B, M, causal, use_sep):
     L.check(L.dense_decoder_mask(_p(cs), _p(mod), _p(out), B, M, 1 if causal else 0, 1 if cs is not None else 0,
                                  1 if use_sep else 0, _stream()))
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# low-rank adapters (csrc/lora.hip)
+# ---------------------------------------------------------------------------------------------
+def _f32_flag(t):
+    if t.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"bf16 or fp32 tensor expected, got {t.dtype}")
+    return 1 if t.dtype == torch.float32 else 0
+
+
+@_timed("lora_apply")
+def lora_apply(x, down, up, y, scale, p_out, R, K, N, backward=False):
+    """P = x down^T, y += scale P up^T, P -> p_out, with down (r, K) / up (N, r) fp32 masters.  backward: the roles are exchanged -
+    x is dY (R, K = out_features), y is dX (R, N = in_features), ``down`` is still lora_down.weight (r, N) and ``up`` lora_up.weight (K, r):
+    dX += scale (dY up) down and p_out receives Q = dY up."""
+    down, up = down.detach(), up.detach()
+    assert down.dtype == up.dtype == p_out.dtype == torch.float32 and down.is_contiguous() and up.is_contiguous() and p_out.is_contiguous()
+    r = down.shape[0]
+    assert up.shape[1] == r and p_out.shape[1] == r and p_out.shape[0] >= R
+    if backward:
+        assert tuple(up.shape) == (K, r) and tuple(down.shape) == (r, N)
+        a, a_sr, a_sk, b, b_sn, b_sr = up, 1, r, down, 1, N
+    else:
+        assert tuple(down.shape) == (r, K) and tuple(up.shape) == (N, r)
+        a, a_sr, a_sk, b, b_sn, b_sr = down, K, 1, up, r, 1
+    assert x.shape[0] >= R and y.shape[0] >= R and x.shape[1] >= K and y.shape[1] >= N
+    L.check(L.lora_apply(_p(x), _ld(x), _p(a), a_sr, a_sk, _p(b), b_sn, b_sr, _p(y), _ld(y), float(scale), _p(p_out), R, K, N, r,
+                         _f32_flag(x), _f32_flag(y), _stream()))
+
+
+@_timed("lora_grad")
+def lora_grad(a, b, out, scale, R, n, transposed=False, accumulate=True):
+    """out (+)= scale a^T b over the first R rows: out (n, r), or (r, n) with ``transposed`` (lora_down.weight's layout)."""
+    out = out.detach()
+    r = b.shape[1]
+    assert b.dtype == out.dtype == torch.float32 and b.is_contiguous() and out.is_contiguous() and b.shape[0] >= R and a.shape[0] >= R
+    assert tuple(out.shape) == ((r, n) if transposed else (n, r)) and a.shape[1] >= n
+    sn, sr = (1, n) if transposed else (r, 1)
+    L.check(L.lora_grad(_p(a), _ld(a), _p(b), _p(out), sn, sr, float(scale), 1 if accumulate else 0, R, n, r, _f32_flag(a), _stream()))

@@ -431,6 +431,7 @@ class GenerationSampler(nn.Module):
                 ops.layernorm_fwd(ctx, blk.context_norm.weight, blk.context_norm.bias, hc, eps=blk.context_norm.eps, R=Rc)
                 kv = ws.get(f"{pre}kv{l}", (Rcp, 2 * D), bf)
                 ops.gemm_nt(hc, eng.w(blk.cross_attn.kv.weight), kv, bias=blk.cross_attn.kv.bias, M=Rc, N=2 * D, K=D)
+                eng._lora_fwd(blk.cross_attn.kv, hc, kv, Rc, None, "ar", "kv")
                 kvc.append(kv)
                 cache.append(ws.get(f"{pre}cache{l}", (B, Tc, 3 * D), bf))
             ya, yb = ws.get(pre + "ya", (Rp, D), f32), ws.get(pre + "yb", (Rp, D), f32)
@@ -447,14 +448,18 @@ class GenerationSampler(nn.Module):
                     ops.layernorm_fwd(y, blk.norm1.weight, blk.norm1.bias, h, eps=blk.norm1.eps, R=B)
                     row = c.view(B, Tc * 3 * D)[:, p * 3 * D:(p + 1) * 3 * D]              # this token's q | k | v inside the cache
                     ops.gemm_nt(h, eng.w(sa.qkv.weight), row, bias=sa.qkv.bias, M=B, N=3 * D, K=D)
+                    eng._lora_fwd(sa.qkv, h, row, B, None, "ar", "qkv")
                     flat = c.view(B * Tc, 3 * D)
                     ops.attn_fwd(row[:, :D], flat[:, D:2 * D], flat[:, 2 * D:], o, B, H, 1, p + 1, eng.scale, kv_batch_rows=Tc,
                                  zero_attn=getattr(blk.self_attn, "allow_zero_attn", False))
                     ops.gemm_nt(o, eng.w(sa.proj.weight), y1, epilogue=L.EPI_RESIDUAL, res=y, bias=sa.proj.bias, M=B, N=D, K=D)
+                    eng._lora_fwd(sa.proj, o, y1, B, None, "ar", "proj")
                     ops.layernorm_fwd(y1, blk.query_norm.weight, blk.query_norm.bias, h, eps=blk.query_norm.eps, R=B)
                     ops.gemm_nt(h, eng.w(xa.q.weight), q2, bias=xa.q.bias, M=B, N=D, K=D)
+                    eng._lora_fwd(xa.q, h, q2, B, None, "ar", "q")
                     ops.attn_fwd(q2, kvc[l][:, :D], kvc[l][:, D:], o, B, H, 1, N, eng.scale, zero_attn=getattr(blk.cross_attn, "allow_zero_attn", False), **emask)
                     ops.gemm_nt(o, eng.w(xa.proj.weight), y2, epilogue=L.EPI_RESIDUAL, res=y1, bias=xa.proj.bias, M=B, N=D, K=D)
+                    eng._lora_fwd(xa.proj, o, y2, B, None, "ar", "proj2")
                     ops.layernorm_fwd(y2, blk.norm2.weight, blk.norm2.bias, h, eps=blk.norm2.eps, R=B)
                     y = yb if y is ya else ya
                     eng._mlp_fwd(blk.mlp, h, y2, y, B, Rp, None, "ar")
