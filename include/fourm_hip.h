@@ -348,6 +348,23 @@ int fm_add_bf16_f32(const void* x, const void* delta, void* out, int64_t n, void
  * gradient copy that enters the branch.  N, ld multiples of 8. */
 int fm_scale_rows_bf16(void* x, int ld, const void* scale, int rows_per_sample, int R, int N, void* stream);
 
+/* Dense front end of FourMViT (fourm/models/fm_vit.py), csrc/vit_embed.hip.
+ * fm_vit_patch_rows: pixels f32 (B, C, H, W) -> rows (B * (H/P) * (W/P), ld): EVERY patch of every image, patches in row-major grid
+ *   order, feature f = (py * P + px) * C + c (upstream's 'b d (nh ph) (nw pw) -> b (nh nw) (ph pw d)').  Rows are bf16 (round to nearest
+ *   even), or f32 copies with rows_f32 (verification mode).  Columns [P*P*C, ld) are written as zero (the K padding of the projection
+ *   GEMM); rows past B * (H/P) * (W/P) are not touched.  A workgroup owns a strip of horizontally adjacent patches: whole image-row
+ *   segments are read contiguously, transposed through LDS and stored 16 bytes per lane.
+ *   Refused (-1): H or W not a multiple of P, ld not a multiple of 8 or smaller than P*P*C, P*P*C > 8192, null pointers, pixels or rows
+ *   not 16-byte aligned.
+ * fm_vit_emb_rows: x[(b * Np + n)][:] = pos[n][:] + mod_emb[:] (all f32; x of row stride ldx): the embedding rows the projection GEMM
+ *   adds onto in place (FM_EPI_RESIDUAL with res == out).  D and ldx multiples of 4, pointers 16-byte aligned.
+ * fm_vit_colsum: db[n] += sum_r dy[r][n] for f32 dy (R, N) of row stride ldy and f32 db: every column summed in double in a fixed order and
+ *   rounded once (deterministic; the bias gradient of encoder_norm from the head's fp32 gradient).  ws: scratch of at least
+ *   min(64, ceil(R / 32)) * N * 8 bytes, 8-byte aligned. */
+int fm_vit_patch_rows(const void* pixels, void* rows, int ld, int B, int C, int H, int W, int P, int rows_f32, void* stream);
+int fm_vit_emb_rows(const void* pos, const void* mod_emb, void* x, int ldx, int B, int Np, int D, void* stream);
+int fm_vit_colsum(const void* dy, int ldy, void* db, int R, int N, void* ws, int64_t ws_bytes, void* stream);
+
 /* Low-rank adapters (LoRAWrapper, fourm/models/lora_utils.py:44-81: y = linear(x) + scale * lora_up(lora_down(x))), csrc/lora.hip.
  * P = x down^T (fp32 accumulation over K), y += scale * P up^T in place (fp32 sum, rounded once to y's type), P written to p_out.
  * x: (R, K) row stride ldx; y: (R, N) row stride ldy; x_f32 / y_f32 select fp32 instead of bf16 elements (bf16 x with fp32 y is

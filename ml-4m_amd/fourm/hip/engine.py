@@ -74,7 +74,7 @@ def check_lora_targets(model):
     ok = set()
     for blk in model.encoder:
         ok |= {id(blk.attn.qkv), id(blk.attn.proj)}
-    for blk in model.decoder:
+    for blk in getattr(model, "decoder", ()):         # (a FourMViT has an encoder only)
         ok |= {id(blk.self_attn.qkv), id(blk.self_attn.proj), id(blk.cross_attn.q), id(blk.cross_attn.kv), id(blk.cross_attn.proj)}
     for name, mod in model.named_modules():
         if not isinstance(mod, LoRAWrapper):
@@ -224,11 +224,13 @@ class FourMEngine:
     # ------------------------------------------------------------------------------------------
     @property
     def device(self):
-        return self.model.mask_token.device
+        t = getattr(self.model, "mask_token", None)
+        return (t if t is not None else next(self.model.parameters())).device
 
     def _unique_params(self):
+        # engine_parameters (FourMViT): the trunk's parameters only - an output head on top is torch's, its gradients come from autograd
         seen, out = set(), []
-        for n, p in self.model.named_parameters():
+        for n, p in getattr(self.model, "engine_parameters", self.model.named_parameters)():
             if id(p) not in seen:
                 seen.add(id(p))
                 out.append((n, p))
@@ -460,10 +462,10 @@ class FourMEngine:
         are trainable is read at every backward."""
         h = getattr(self, "_hoist_ctx", None)
         if h is None:
-            m = self.model
-            h = HOIST_CTX and len(m.decoder) > 0 and all(
+            dec = getattr(self.model, "decoder", ())
+            h = HOIST_CTX and len(dec) > 0 and all(
                 not isinstance(b.context_norm.bias, nn.Parameter) and b.cross_attn.kv.bias is None and not is_lora(b.cross_attn.kv)
-                for b in m.decoder)
+                for b in dec)
             self._hoist_ctx = h
         return h
 

@@ -103,7 +103,7 @@ _BLOCK_OWNER = weakref.WeakKeyDictionary()
 
 def register_blocks(model):
     ref = weakref.ref(model)
-    for blk in list(model.encoder) + list(model.decoder):
+    for blk in list(model.encoder) + list(getattr(model, "decoder", ())):
         _BLOCK_OWNER[blk] = ref
 
 

@@ -583,6 +583,29 @@ def dense_decoder_mask(cs, mod, B, M, causal, use_sep):
 
 
 # ---------------------------------------------------------------------------------------------
+# dense ViT front end (csrc/vit_embed.hip)
+# ---------------------------------------------------------------------------------------------
+def vit_patch_rows(pixels, rows, P):
+    """rows[(b, gy, gx)][(py, px, c)] <- pixels (B, C, H, W) fp32: every patch in grid order; rows bf16 or fp32, pad columns zeroed."""
+    B, C, H, W = pixels.shape
+    assert pixels.dtype == torch.float32 and pixels.is_contiguous() and rows.dtype in (torch.bfloat16, torch.float32)
+    assert rows.shape[0] >= B * (H // P) * (W // P)
+    with _prof("vit_patch_rows", 0.0, pixels.numel() * 4.0 + B * (H // P) * (W // P) * _ld(rows) * rows.element_size()):
+        L.check(L.vit_patch_rows(_p(pixels), _p(rows), _ld(rows), B, C, H, W, P, 1 if rows.dtype == torch.float32 else 0, _stream()))
+    return rows
+
+
+def vit_emb_rows(pos, mod_emb, x, B, Np):
+    """x[(b, n)] = pos[n] + mod_emb (fp32): the rows the patch projection is added onto (gemm_nt, EPI_RESIDUAL in place)."""
+    D = mod_emb.numel()
+    pos, mod_emb = pos.detach(), mod_emb.detach()
+    assert pos.dtype == mod_emb.dtype == x.dtype == torch.float32 and pos.is_contiguous() and pos.numel() == Np * D and x.shape[0] >= B * Np
+    with _prof("vit_emb_rows", 0.0, 4.0 * B * Np * D):
+        L.check(L.vit_emb_rows(_p(pos), _p(mod_emb), _p(x), _ld(x), B, Np, D, _stream()))
+    return x
+
+
+# ---------------------------------------------------------------------------------------------
 # low-rank adapters (csrc/lora.hip)
 # ---------------------------------------------------------------------------------------------
 def _f32_flag(t):
@@ -620,3 +643,13 @@ def lora_grad(a, b, out, scale, R, n, transposed=False, accumulate=True):
     assert tuple(out.shape) == ((r, n) if transposed else (n, r)) and a.shape[1] >= n
     sn, sr = (1, n) if transposed else (r, 1)
     L.check(L.lora_grad(_p(a), _ld(a), _p(b), _p(out), sn, sr, float(scale), 1 if accumulate else 0, R, n, r, _f32_flag(a), _stream()))
+
+
+def vit_colsum(dy, db, ws, R=None):
+    """db[n] += sum_r dy[r][n] (fp32 dy and db), every column summed in double in a fixed order and rounded once.  ``ws``: float64 scratch
+    of at least 64 * N elements."""
+    R, N = dy.shape[0] if R is None else R, db.numel()
+    assert dy.dtype == db.dtype == torch.float32 and ws.dtype == torch.float64 and db.is_contiguous() and dy.shape[0] >= R and dy.shape[1] >= N
+    with _prof("colsum", 0.0, 4.0 * R * N):
+        L.check(L.vit_colsum(_p(dy), _ld(dy), _p(db), R, N, _p(ws), ws.numel() * 8, _stream()))
+    return db
