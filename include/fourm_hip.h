@@ -199,6 +199,36 @@ int fm_attn_bwd(const fm_attn_args* args, void* stream);   /* any Nq, Nk (single
 void fm_set_attn_transpose_read(int on);
 int fm_get_attn_transpose_read(void);
 
+/* Single-query attention of one cached decoder layer (csrc/attn_decode.hip): the whole attention step of incremental decoding in
+ * one launch, for every trunk variant - NormAttention / NormCrossAttention (fm_utils.py:222-261) included.
+ * One query row per sample, head_dim 64, head h in columns [64h, 64h + 64).  q: (B) rows of stride ldq; k, v: views of row strides
+ * ldk / ldv whose sample b starts at row b * kv_batch_rows (0 = Nk, the fm_attn_args convention) - e.g. the k and v column blocks
+ * of a (B, T, 3 D) q | k | v cache; the first Nk rows of a sample are attended to, nothing else of k / v is read.  is_f32 selects
+ * fp32 instead of bf16 elements for q, k, v and o alike.
+ * Head norm (q_w != NULL; q_w, q_b, k_w, k_b: f32 (64), the biases may be NULL): LayerNorm over the 64 features of a head with eps.
+ *   q is normalised on chip and never written back.  k_new_row >= 0: the key in row k_new_row of every sample is normalised (k_w
+ *   required), WRITTEN BACK in place in the storage type and used as that stored (rounded) value - the cache then holds normalised
+ *   keys and later tokens read them as they are.  k_new_row < 0: every key is taken as already normalised (cross-attention over
+ *   context keys normalised once).  The statistics and the affine map are evaluated in double and rounded once, so the stored key is
+ *   the correctly rounded LayerNorm also where x - mean cancels.  Without q_w no byte of k is written, whatever k_new_row says.
+ * Scores scale * q.k_j in fp32 (64 fused multiply-adds in feature order); kpad (optional): (B, Nk) uint8, 1 = blocked: the score is
+ *   REPLACED by -finfo(bf16).max (-finfo(float32).max with is_f32) as in fm_attn_fwd / fm_attn_f32_fwd, so a fully blocked sample
+ *   attends uniformly.  Softmax in fp32, or softmax1 with zero_attn (fm_attn_args.zero_attn).  o = sum_j p_j v_j in fp32, rounded once.
+ * One workgroup per (sample, head); workgroups share nothing; the result is bit-reproducible.
+ * Refused (-1): null q / k / v / o; B, H < 1; Nk < 1 or > FM_ATTN_DECODE_MAX_NK; kv_batch_rows < Nk with B > 1; k_new_row >= Nk; a norm
+ * on k_new_row without k_w; a row stride below 64 H; k / v not 16-byte aligned or ldk / ldv not a multiple of 16 bytes; q / o / the
+ * norm vectors not aligned to their element. */
+#define FM_ATTN_DECODE_MAX_NK 8192
+typedef struct fm_attn_decode_args {
+    const void* q; void* k; const void* v; void* o;
+    const void* q_w; const void* q_b; const void* k_w; const void* k_b;
+    const void* kpad;
+    int32_t ldq, ldk, ldv, ldo;
+    int32_t B, H, Nk, kv_batch_rows, k_new_row, is_f32, zero_attn, pad_;
+    float scale, eps;
+} fm_attn_decode_args;
+int fm_attn_decode(const fm_attn_decode_args* args, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Token selection + embedding  (encoder: fm.py:245-277,338-390 + encoder_embeddings.py forward()s;
  * decoder: fm.py:279-336,392-438 + decoder_embeddings.py forward_embed()s)

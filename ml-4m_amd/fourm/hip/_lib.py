@@ -76,6 +76,13 @@ class AttnArgs(C.Structure):
                 ("lddo", i32), ("lddq", i32), ("lddk", i32), ("lddv", i32), ("force_tr", i32), ("kv_batch_rows", i32), ("zero_attn", i32)]
 
 
+class AttnDecodeArgs(C.Structure):
+    _fields_ = [("q", vp), ("k", vp), ("v", vp), ("o", vp), ("q_w", vp), ("q_b", vp), ("k_w", vp), ("k_b", vp), ("kpad", vp),
+                ("ldq", i32), ("ldk", i32), ("ldv", i32), ("ldo", i32),
+                ("B", i32), ("H", i32), ("Nk", i32), ("kv_batch_rows", i32), ("k_new_row", i32), ("is_f32", i32), ("zero_attn", i32), ("pad_", i32),
+                ("scale", f32), ("eps", f32)]
+
+
 class ModDesc(C.Structure):
     _fields_ = [("ids", vp), ("mask", vp), ("dam", vp), ("table", vp), ("pos", vp), ("mod_emb", vp), ("proj_bias", vp),
                 ("L", i32), ("kind", i32), ("ids_are_i64", i32), ("mod_id", i32), ("max_len", i32), ("shifted", i32),
@@ -155,6 +162,8 @@ layernorm_bwd = _sig("fm_layernorm_bwd", vp, i32, vp, vp, i32, vp, vp, vp, vp, v
 layernorm_bwd_h = _sig("fm_layernorm_bwd_h", vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, vp, i32, vp, i32, i32, vp)
 attn_fwd = _sig("fm_attn_fwd", P(AttnArgs), vp)
 attn_bwd = _sig("fm_attn_bwd", P(AttnArgs), vp)
+attn_decode = _sig("fm_attn_decode", P(AttnDecodeArgs), vp)
+ATTN_DECODE_MAX_NK = 8192      # FM_ATTN_DECODE_MAX_NK
 select_embed = _sig("fm_select_embed", P(SelectDesc), vp)
 embed_bwd = _sig("fm_embed_bwd", P(EmbedBwdDesc), vp)
 dense_decoder_mask = _sig("fm_dense_decoder_mask", vp, vp, vp, i32, i32, i32, i32, i32, vp)
@@ -244,7 +253,7 @@ lora_grad = _sig("fm_lora_grad", vp, i32, vp, vp, i64, i64, f32, i32, i32, i32, 
 vit_patch_rows = _sig("fm_vit_patch_rows", vp, vp, i32, i32, i32, i32, i32, i32, i32, vp)
 vit_emb_rows = _sig("fm_vit_emb_rows", vp, vp, vp, i32, i32, i32, i32, vp)
 vit_colsum = _sig("fm_vit_colsum", vp, i32, vp, i32, i32, vp, i64, vp)
-EXPORTS = ["fm_vit_patch_rows", "fm_vit_emb_rows", "fm_vit_colsum", "fm_lora_apply", "fm_lora_grad", "fm_vq_assign_wide", "fm_memcodes_assign", "fm_convnext_block", "fm_split3_bf16", "fm_unet_im2col", "fm_groupnorm_nhwc", "fm_add_bf16", "fm_silu_f32_to_bf16", "fm_timestep_embedding", "fm_unet_attention", "fm_diffusion_x0", "fm_quantile_abs",
+EXPORTS = ["fm_attn_decode", "fm_vit_patch_rows", "fm_vit_emb_rows", "fm_vit_colsum", "fm_lora_apply", "fm_lora_grad", "fm_vq_assign_wide", "fm_memcodes_assign", "fm_convnext_block", "fm_split3_bf16", "fm_unet_im2col", "fm_groupnorm_nhwc", "fm_add_bf16", "fm_silu_f32_to_bf16", "fm_timestep_embedding", "fm_unet_attention", "fm_diffusion_x0", "fm_quantile_abs",
            "fm_diffusion_step", "fm_unpack_image_u8", "fm_unpack_ids_u16", "fm_unpack_mask_bits", "fm_decoder_attention_from_target", "fm_guidance_combine", "fm_image_mask", "fm_token_budgets", "fm_span_mask", "fm_vq_code_stats", "fm_vq_ema_update", "fm_vq_code_bias", "fm_vq_assign_bias", "fm_vq_code_stats_raw", "fm_vq_ema_update_euclid", "fm_vq_unpatchify", "fm_vq_latent_grad", "fm_tanh_bwd_f32", "fm_embed_rows_f32", "fm_vq_patchify_ex", "fm_vq_cls_emb_bwd", "fm_vq_latent_grad_normalized", "fm_abi_version", "fm_last_error", "fm_gemm_nt", "fm_set_gemm_nt_config", "fm_get_gemm_nt_config", "fm_set_reserved_cus", "fm_get_reserved_cus", "fm_bf16_to_f32_scaled", "fm_add_bf16_f32", "fm_scale_rows_bf16", "fm_gemm_tn", "fm_gemm_tn_multi", "fm_set_gemm_tn_config", "fm_get_gemm_tn_config", "fm_set_tn_transpose_read",
            "fm_get_tn_transpose_read", "fm_layernorm_fwd", "fm_layernorm_fwd_res", "fm_layernorm_bwd", "fm_layernorm_bwd_h", "fm_headnorm_fwd", "fm_headnorm_bwd", "fm_attn_fwd", "fm_attn_bwd",
            "fm_set_attn_transpose_read", "fm_get_attn_transpose_read", "fm_select_embed", "fm_embed_bwd",

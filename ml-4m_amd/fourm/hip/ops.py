@@ -374,6 +374,30 @@ def attn_fwd(q, k, v, o, B, H, Nq, Nk, scale, *, mask_kind=L.MASK_NONE, kpad=Non
     return o
 
 
+@_timed("attn_decode")
+def attn_decode(q, k, v, o, B, H, Nk, scale, *, kv_batch_rows=0, k_new_row=-1, q_norm=None, k_norm=None, eps=1e-6, kpad=None, zero_attn=False):
+    """One query row per sample against the first Nk rows of its keys / values (fm_attn_decode): q (B, >= 64 H), k / v 2-D views whose
+    sample b starts at row b * kv_batch_rows, o (>= B, >= 64 H); all four bf16 or all four fp32.  q_norm / k_norm: (weight, bias | None)
+    of the per-head LayerNorm; with q_norm given and k_new_row >= 0 the key in that row of every sample is normalised IN PLACE."""
+    a = L.AttnDecodeArgs()
+    a.q, a.k, a.v, a.o = _p(q), _p(k), _p(v), _p(o)
+    if not (q.dtype == k.dtype == v.dtype == o.dtype) or q.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError("attn_decode: q, k, v, o must share one of bf16 / fp32")
+    for w in (q_norm or ()) + (k_norm or ()):
+        if w is not None and (w.dtype != torch.float32 or w.numel() != 64 or not w.is_contiguous()):
+            raise TypeError("attn_decode: norm vectors are contiguous fp32 (64)")
+    a.q_w, a.q_b = (_p(q_norm[0]), _p(q_norm[1])) if q_norm is not None else (None, None)
+    a.k_w, a.k_b = (_p(k_norm[0]), _p(k_norm[1])) if k_norm is not None else (None, None)
+    if kpad is not None and (kpad.dtype not in (torch.bool, torch.uint8) or kpad.shape != (B, Nk) or not kpad.is_contiguous()):
+        raise TypeError("attn_decode: kpad is a contiguous (B, Nk) bool / uint8 tensor")
+    a.kpad = _p(kpad)
+    a.ldq, a.ldk, a.ldv, a.ldo = _ld(q), _ld(k), _ld(v), _ld(o)
+    a.B, a.H, a.Nk, a.kv_batch_rows, a.k_new_row = B, H, Nk, kv_batch_rows, k_new_row
+    a.is_f32, a.zero_attn, a.scale, a.eps = int(q.dtype == torch.float32), 1 if zero_attn else 0, scale, eps
+    L.check(L.attn_decode(C.byref(a), _stream()))
+    return o
+
+
 def attn_bwd(q, k, v, o, do, dq, dk, dv, B, H, Nq, Nk, scale, stat_m, stat_l, *, mask_kind=L.MASK_NONE, kpad=None, cs=None,
              modq=None, modk=None, dense=None, causal=False, force_tr=-1, zero_attn=False):
     a = _attn_args(q, k, v, o, B, H, Nq, Nk, scale, mask_kind, kpad, cs, modq, modk, dense, causal, stat_m, stat_l, force_tr, zero_attn)

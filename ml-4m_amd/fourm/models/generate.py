@@ -361,6 +361,9 @@ class GenerationSampler(nn.Module):
         layer keeps the prefix's q | k | v rows in a (B, T_max, 3 D) cache the qkv GEMM writes into directly, the new token attends
         to the filled part of it (fm_attn_fwd, kv_batch_rows = T_max), and the cross-attention keys / values of the encoded
         context are computed once per layer: one token costs one pass over B rows instead of B * prefix rows.
+        qk_norm models (NormAttention / NormCrossAttention) and the fp32 verification mode run both attention steps of a layer on
+        fm_attn_decode instead: the query is normalised on chip, the new token's key is normalised and written back into the cache
+        (which therefore holds NORMALISED keys), the context keys are normalised once per layer - the same number of launches per token.
         With ``conditioning`` and ``guidance_scale != 1`` a second decoder state runs on the context of the emptied conditioning
         (classifier-free guidance, generate.py:919-1027) and the last-token logits are combined in fp32.
         ``uniforms`` (steps, B) fixes the random draws (one per sampled token).
@@ -374,9 +377,9 @@ class GenerationSampler(nn.Module):
         demb = m.decoder_embeddings[target_mod]
         if demb.kind != L.KIND_SEQ:
             raise NotImplementedError("autoregressive decoding is for sequence modalities (grid tokens: MaskGIT / ROAR steps)")
-        if eng.qk_norm or eng.fp32:
-            raise NotImplementedError("the K/V-cache decode path covers the bf16 models without qk_norm")
-        D, H, ws, bf, f32 = eng.D, eng.H, eng.ws, eng.adt, torch.float32
+        D, H, ws, adt, f32 = eng.D, eng.H, eng.ws, eng.adt, torch.float32
+        fused = eng.qk_norm or eng.fp32                              # fm_attn_decode; the bf16 trunks without qk_norm keep fm_attn_fwd
+        qkn = (lambda n: (n.weight, n.bias)) if eng.qk_norm else (lambda n: None)
         guided = len(conditioning) > 0 and float(guidance_scale) != 1.0
         if target_mod in conditioning:
             raise ValueError("the target modality cannot be part of the conditioning that is dropped")
@@ -414,7 +417,7 @@ class GenerationSampler(nn.Module):
         V = w_logits.shape[0]
 
         def make_decoder(cond_dict, slot):
-            """Encode ``cond_dict`` once; -> decode(tok (B,), p) = logits (B, V) bf16 predicting position p + 1, with this context's
+            """Encode ``cond_dict`` once; -> decode(tok (B,), p) = logits (B, V) (bf16; fp32 in fp32 mode) predicting position p + 1, with this context's
             own per-layer K/V cache (workspace names carry ``slot``: the guided run keeps two of them alive)."""
             names = [k for k in cond_dict if k in m.encoder_embeddings]
             vis = sum((~cond_dict[k]["input_mask"].reshape(B, -1).bool()).sum(1) for k in names)
@@ -426,19 +429,27 @@ class GenerationSampler(nn.Module):
             N, Rc, Rcp = n_enc, B * n_enc, ctx.shape[0]
             pre = f"ar{slot}."
             kvc, cache = [], []
-            hc = ws.get(pre + "hc", (Rcp, D), bf)
+            hc = ws.get(pre + "hc", (Rcp, D), adt)
+            kstat = ws.get(pre + "kstat", (Rcp * H, 2), f32) if eng.qk_norm else None
             for l, blk in enumerate(m.decoder):                      # context keys / values once per layer, an empty q|k|v cache
                 ops.layernorm_fwd(ctx, blk.context_norm.weight, blk.context_norm.bias, hc, eps=blk.context_norm.eps, R=Rc)
-                kv = ws.get(f"{pre}kv{l}", (Rcp, 2 * D), bf)
+                kv = ws.get(f"{pre}kv{l}", (Rcp, 2 * D), adt)
                 ops.gemm_nt(hc, eng.w(blk.cross_attn.kv.weight), kv, bias=blk.cross_attn.kv.bias, M=Rc, N=2 * D, K=D)
                 eng._lora_fwd(blk.cross_attn.kv, hc, kv, Rc, None, "ar", "kv")
-                kvc.append(kv)
-                cache.append(ws.get(f"{pre}cache{l}", (B, Tc, 3 * D), bf))
+                xk = kv[:, :D]
+                if eng.qk_norm:                                      # the context keys are normalised once, not once per token
+                    xa = blk.cross_attn
+                    if blk.self_attn.q_norm.eps != blk.self_attn.k_norm.eps or xa.q_norm.eps != xa.k_norm.eps:
+                        raise NotImplementedError("q_norm and k_norm of one attention with different eps")
+                    xk = ws.get(f"{pre}kn{l}", (Rcp, D), adt)
+                    ops.headnorm_fwd(kv[:, :D], xa.k_norm.weight, xa.k_norm.bias, xk, kstat, Rc, H, xa.k_norm.eps)
+                kvc.append((xk, kv[:, D:]))
+                cache.append(ws.get(f"{pre}cache{l}", (B, Tc, 3 * D), adt))
             ya, yb = ws.get(pre + "ya", (Rp, D), f32), ws.get(pre + "yb", (Rp, D), f32)
-            h, o = ws.get(pre + "h", (Rp, D), bf), ws.get(pre + "o", (Rp, D), bf)
+            h, o = ws.get(pre + "h", (Rp, D), adt), ws.get(pre + "o", (Rp, D), adt)
             y1, y2 = ws.get(pre + "y1", (Rp, D), f32), ws.get(pre + "y2", (Rp, D), f32)
-            q2 = ws.get(pre + "q2", (Rp, D), bf)
-            lg = ws.get(pre + "logits", (Rp, ops.ru(V, 8)), bf)
+            q2 = ws.get(pre + "q2", (Rp, D), adt)
+            lg = ws.get(pre + "logits", (Rp, ops.ru(V, 8)), adt)
 
             def decode(tok, p):
                 y = ya
@@ -450,14 +461,25 @@ class GenerationSampler(nn.Module):
                     ops.gemm_nt(h, eng.w(sa.qkv.weight), row, bias=sa.qkv.bias, M=B, N=3 * D, K=D)
                     eng._lora_fwd(sa.qkv, h, row, B, None, "ar", "qkv")
                     flat = c.view(B * Tc, 3 * D)
-                    ops.attn_fwd(row[:, :D], flat[:, D:2 * D], flat[:, 2 * D:], o, B, H, 1, p + 1, eng.scale, kv_batch_rows=Tc,
-                                 zero_attn=getattr(blk.self_attn, "allow_zero_attn", False))
+                    if fused:                                        # (q_norm on chip, k_norm of row p written back into the cache)
+                        ops.attn_decode(row[:, :D], flat[:, D:2 * D], flat[:, 2 * D:], o, B, H, p + 1, eng.scale, kv_batch_rows=Tc,
+                                        k_new_row=p if eng.qk_norm else -1, q_norm=qkn(getattr(sa, "q_norm", None)),
+                                        k_norm=qkn(getattr(sa, "k_norm", None)), eps=sa.q_norm.eps if eng.qk_norm else 0.0,
+                                        zero_attn=getattr(sa, "allow_zero_attn", False))
+                    else:
+                        ops.attn_fwd(row[:, :D], flat[:, D:2 * D], flat[:, 2 * D:], o, B, H, 1, p + 1, eng.scale, kv_batch_rows=Tc,
+                                     zero_attn=getattr(blk.self_attn, "allow_zero_attn", False))
                     ops.gemm_nt(o, eng.w(sa.proj.weight), y1, epilogue=L.EPI_RESIDUAL, res=y, bias=sa.proj.bias, M=B, N=D, K=D)
                     eng._lora_fwd(sa.proj, o, y1, B, None, "ar", "proj")
                     ops.layernorm_fwd(y1, blk.query_norm.weight, blk.query_norm.bias, h, eps=blk.query_norm.eps, R=B)
                     ops.gemm_nt(h, eng.w(xa.q.weight), q2, bias=xa.q.bias, M=B, N=D, K=D)
                     eng._lora_fwd(xa.q, h, q2, B, None, "ar", "q")
-                    ops.attn_fwd(q2, kvc[l][:, :D], kvc[l][:, D:], o, B, H, 1, N, eng.scale, zero_attn=getattr(blk.cross_attn, "allow_zero_attn", False), **emask)
+                    if fused:                                        # (the context keys are already normalised)
+                        ops.attn_decode(q2, kvc[l][0], kvc[l][1], o, B, H, N, eng.scale, q_norm=qkn(getattr(xa, "q_norm", None)),
+                                        eps=xa.q_norm.eps if eng.qk_norm else 0.0, kpad=emask["kpad"],
+                                        zero_attn=getattr(xa, "allow_zero_attn", False))
+                    else:
+                        ops.attn_fwd(q2, kvc[l][0], kvc[l][1], o, B, H, 1, N, eng.scale, zero_attn=getattr(blk.cross_attn, "allow_zero_attn", False), **emask)
                     ops.gemm_nt(o, eng.w(xa.proj.weight), y2, epilogue=L.EPI_RESIDUAL, res=y1, bias=xa.proj.bias, M=B, N=D, K=D)
                     eng._lora_fwd(xa.proj, o, y2, B, None, "ar", "proj2")
                     ops.layernorm_fwd(y2, blk.norm2.weight, blk.norm2.bias, h, eps=blk.norm2.eps, R=B)
