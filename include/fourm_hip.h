@@ -497,6 +497,30 @@ int fm_cross_entropy_f32(void* logits, int ldl, const int32_t* perm, const int32
                          int write_grad, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * fp32 compute mode of the diffusion detokenizer (csrc/unet_f32.hip): the non-GEMM kernels of csrc/unet.hip (declared further down) once
+ * more with f32 feature maps and no bf16 rounding - compute_precision = "fp32" on PatchedUNetCondCat / DiVAE.  Same semantics, index rules
+ * and conventions as their bf16 counterparts; every activation pointer is f32, every convolution and Linear of this mode is fm_gemm_f32 (a
+ * 3 x 3 convolution behind the im2col below).  Plain kernels, not the hot path; fixed summation orders (bit-reproducible).
+ * ---------------------------------------------------------------------------------------------- */
+/* The bf16 im2col with f32 rows: same arguments and index rules (two sources, ksize 1 | 3, stride 1 | 2, up1, the fp32 nearest rule
+ * min(floor(fp32(i) * fp32(n_in) / fp32(n_out)), n_in - 1) for src2).  C1, C2, ld1, ld2, ldo and kpad are multiples of 4 (no 64-column
+ * padding in this mode); columns [ksize^2 (C1 + C2), kpad) are zeroed, nothing is written at or beyond column kpad. */
+int fm_unet_im2col_f32(const void* src1, int ld1, int C1, const void* src2, int ld2, int C2, int H2, int W2, void* out, int ldo, int kpad,
+                       int B, int H, int W, int ksize, int stride, int up1, void* stream);
+/* y = [silu] GroupNorm_groups(x + add[b][c]) * w + b over f32 rows (B, HW, C), f32 result: two-pass statistics per (sample, group) - the
+ * mean, then the squared deviations about it - in a fixed order.  add f32 (B, >= C) with row stride ld_add, or NULL.  Any C that is a
+ * multiple of groups, C <= 1024; needs no scratch. */
+int fm_groupnorm_nhwc_f32(const void* x, int ldx, const void* add, int ld_add, const void* w, const void* b, void* y, int ldy, int B, int HW, int C,
+                          int groups, float eps, int silu, void* stream);
+/* QKVAttentionLegacy on f32 qkv rows (B * T, ld): per head [q | k | v] of ch channels, q and k each scaled by ch^-1/4, fp32 softmax;
+ * out f32 (B * T, ldo).  ch % 4 == 0, ld % 4 == 0, (ch + T) * 4 bytes <= 60 KB of LDS. */
+int fm_unet_attention_f32(const void* qkv, int ld, void* out, int ldo, int B, int T, int heads, int ch, void* stream);
+int fm_add_f32(const void* a, int lda, const void* b, int ldb, void* out, int ldo, int64_t rows, int C, void* stream);   /* out = a + b, f32 rows with row strides */
+int fm_silu_f32(const void* x, void* y, int64_t n, void* stream);                                                        /* y = x * sigmoid(x), f32 to f32 */
+/* out[b] = [cos(t_b f_i) | sin(t_b f_i)], f_i = exp(-ln(max_period) i / (dim / 2)); t f32 (B), out f32 (B, ldo)   (nn.py:120-140) */
+int fm_timestep_embedding_f32(const void* t, void* out, int ldo, int B, int dim, float max_period, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * VQ tokenizer front end (fourm/vq/vqvae.py:302-331)
  * ---------------------------------------------------------------------------------------------- */
 /* out[(b*G + g)][c*P*P + py*P + px] (bf16, row stride ld_out, pad zero) <- img (B, C, H, W) f32: the operand

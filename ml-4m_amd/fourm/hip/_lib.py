@@ -245,6 +245,13 @@ add_bf16 = _sig("fm_add_bf16", vp, i32, vp, i32, vp, i32, i64, i32, vp)
 silu_f32_to_bf16 = _sig("fm_silu_f32_to_bf16", vp, vp, i64, vp)
 timestep_embedding = _sig("fm_timestep_embedding", vp, vp, i32, i32, i32, f32, vp)
 unet_attention = _sig("fm_unet_attention", vp, i32, vp, i32, i32, i32, i32, i32, vp)
+# fp32 compute mode of the diffusion detokenizer (csrc/unet_f32.hip)
+unet_im2col_f32 = _sig("fm_unet_im2col_f32", vp, i32, i32, vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp)
+groupnorm_nhwc_f32 = _sig("fm_groupnorm_nhwc_f32", vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp)
+unet_attention_f32 = _sig("fm_unet_attention_f32", vp, i32, vp, i32, i32, i32, i32, i32, vp)
+add_f32 = _sig("fm_add_f32", vp, i32, vp, i32, vp, i32, i64, i32, vp)
+silu_f32 = _sig("fm_silu_f32", vp, vp, i64, vp)
+timestep_embedding_f32 = _sig("fm_timestep_embedding_f32", vp, vp, i32, i32, i32, f32, vp)
 diffusion_x0 = _sig("fm_diffusion_x0", vp, vp, f32, f32, vp, i64, vp)
 quantile_abs = _sig("fm_quantile_abs", vp, i32, i64, f32, vp, vp)
 diffusion_step = _sig("fm_diffusion_step", vp, vp, f32, f32, vp, vp, vp, f32, f32, f32, f32, vp, vp, i32, i64, vp)
@@ -261,7 +268,8 @@ EXPORTS = ["fm_attn_decode", "fm_vit_patch_rows", "fm_vit_emb_rows", "fm_vit_col
            "fm_gelu_bwd", "fm_cast_pad", "fm_transpose_cast_pad", "fm_shadow_refresh", "fm_fold_colscale_grad", "fm_colsum", "fm_f32_to_bf16", "fm_adamw", "fm_adamw_shadow",
            "fm_sumsq", "fm_clip_coef", "fm_vq_patchify", "fm_l2norm_rows", "fm_vq_assign",
            "fm_sample_tokens", "fm_maskgit_commit", "fm_gemm_f32", "fm_attn_f32_fwd", "fm_attn_f32_bwd", "fm_layernorm_bwd_f32", "fm_headnorm_f32_fwd", "fm_headnorm_f32_bwd",
-           "fm_swiglu_bwd_f32", "fm_gelu_bwd_f32", "fm_colsum_f32", "fm_cross_entropy_f32", "fm_lab_set"]
+           "fm_swiglu_bwd_f32", "fm_gelu_bwd_f32", "fm_colsum_f32", "fm_cross_entropy_f32", "fm_lab_set",
+           "fm_unet_im2col_f32", "fm_groupnorm_nhwc_f32", "fm_unet_attention_f32", "fm_add_f32", "fm_silu_f32", "fm_timestep_embedding_f32"]
 
 
 def check(rc: int):

@@ -25,7 +25,14 @@ class _VitEngine(FourMEngine):
         if self.D // self.H != 64:
             raise NotImplementedError("the HIP attention kernels are built for head_dim 64")
         self.gated, self.act, self.qk_norm = False, "gelu", False
-        self.fp32, self.adt = False, torch.bfloat16       # the 12 blocks follow autocast; the post-MLP / projection call the fp32 GEMM
+        # "bf16": the 12 blocks follow autocast; the post-MLP / projection call the fp32 GEMM.  "fp32" (VQ.compute_precision): f32 patch rows and
+        # blocks on the trunk's fp32 kernels (csrc/fp32_verify.hip) - upstream's fp32 tokenizer run.  The attribute of the ENCODER decides; the
+        # FOURM_PRECISION environment variable of the trunk is not consulted.
+        prec = getattr(enc, "compute_precision", "bf16")
+        if prec not in ("bf16", "fp32"):
+            raise ValueError(f"compute_precision {prec!r}: 'bf16' or 'fp32'")
+        self.precision = prec
+        self.fp32, self.adt = prec == "fp32", torch.float32 if prec == "fp32" else torch.bfloat16
         self.Hd = blk.mlp.hidden_features
         self.Hp = ru(self.Hd, 64)
         self.scale, self.eps = 64 ** -0.5, blk.norm1.eps
@@ -67,7 +74,7 @@ class _VitEngine(FourMEngine):
 def _engine(enc) -> _VitEngine:
     eng = getattr(enc, "_hip_engine", None)
     dev = enc.blocks[0].norm1.weight.device
-    if eng is None or eng.device != dev:
+    if eng is None or eng.device != dev or eng.precision != getattr(enc, "compute_precision", "bf16"):      # (a new engine: scratch and cached operands of the other precision go)
         if dev.type != "cuda":
             raise RuntimeError("the tokenizer computes on an MI355X through libfourm_hip.so; move it to the GPU first")
         eng = _VitEngine(enc)
@@ -138,7 +145,7 @@ def _post_mlp_fwd(eng, vit, stream, R, st, prefix):
     ops.layernorm_fwd(stream, vit.norm_mlp.weight, vit.norm_mlp.bias, n, mu, rs, eps=vit.norm_mlp.eps, R=R)
     hid = vit.post_mlp.fc1.weight.shape[0]
     out = ws.get(prefix + ".post", (Rp, D), f32)
-    if st is None and SPLIT3_TAIL and D % 64 == 0 and hid % 64 == 0:
+    if st is None and SPLIT3_TAIL and not eng.fp32 and D % 64 == 0 and hid % 64 == 0:
         bf = torch.bfloat16
         n3 = ws.get(prefix + ".n3", (Rp, 3 * D), bf)
         L.check(L.split3_bf16(ops._p(n), D, ops._p(n3), 3 * D, R, D, 0, 0, ops._stream()))
@@ -174,6 +181,14 @@ def _tokens(enc, x, st=None, prep=None):
     Rp = ru(R, 128)
     x = x.long().contiguous() if labels else x.float().contiguous()
     feat = C * P * P
+    if eng.fp32:
+        if st is not None:
+            raise NotImplementedError("compute_precision = 'fp32' is inference only: the tokenizer's training forward / backward run in bf16 mode")
+        stream = _patch_proj_f32(eng, enc, x, prep, labels, (B, C, Hh, Ww), P, Rp)
+        stream = _blocks_fwd(eng, enc, stream, B, G, None, "vit")
+        if hasattr(enc, "post_mlp"):
+            stream = _post_mlp_fwd(eng, enc, stream, R, None, "vq")
+        return eng, stream, (B, nh, nw)
     patches = ws.get("vq.patches", (Rp, ru(feat, 64)), torch.bfloat16)
     if prep is None:
         L.check(L.vq_patchify(ops._p(x), ops._p(patches), patches.stride(0), B, C, Hh, Ww, P, ops._stream()))
@@ -190,6 +205,30 @@ def _tokens(enc, x, st=None, prep=None):
     if hasattr(enc, "post_mlp"):
         stream = _post_mlp_fwd(eng, enc, stream, R, st, "vq")
     return eng, stream, (B, nh, nw)
+
+
+def _patch_proj_f32(eng, enc, x, prep, labels, shape, P, Rp):
+    """fp32 mode: upstream's prepare_input arithmetic and the patch rearrange in torch (plumbing), then the patch projection + position table
+    as one fm_gemm_f32 on f32 rows 'b c (nh ph) (nw pw) -> (b nh nw) (c ph pw)' against the f32 master of enc.proj.weight."""
+    B, C, Hh, Ww = shape
+    nh, nw = Hh // P, Ww // P
+    R, feat, f32 = B * nh * nw, C * P * P, torch.float32
+    if labels:                                          # cls_emb(x): (B, H, W) -> (B, C, H, W)   [vqvae.py:280-284]
+        img = torch.nn.functional.embedding(x, prep["cls_emb"].detach().to(f32)).permute(0, 3, 1, 2)
+    elif prep is not None and prep.get("mean_std") is not None:
+        # 2 * denormalize(x) - 1 in upstream's own order   [vqvae.py:282-283; utils/misc.py:23-36: (x - mean') / std' with mean' = -m / s, std' = 1 / s]
+        mean, std = prep["mean_std"]
+        m2 = torch.tensor([-m / s for m, s in zip(mean, std)], dtype=f32, device=x.device).view(1, -1, 1, 1)
+        s2 = torch.tensor([1 / s for s in std], dtype=f32, device=x.device).view(1, -1, 1, 1)
+        img = 2.0 * ((x - m2) / s2) - 1.0
+    else:
+        img = x
+    patches = eng.ws.get("vq.patches32", (Rp, feat), f32)
+    patches[:R].view(B, nh, nw, C, P, P).copy_(img.contiguous().view(B, C, nh, P, nw, P).permute(0, 2, 4, 1, 3, 5))
+    pos = _pos_rows(eng, enc, B, nh, nw, Rp)
+    stream = eng.ws.get("vq.x0", (Rp, eng.D), f32)
+    ops.gemm_nt(patches, eng.w(enc.proj.weight), stream, epilogue=L.EPI_RESIDUAL, res=pos, bias=enc.proj.bias, M=R, N=eng.D, K=feat)
+    return stream
 
 
 @torch.no_grad()

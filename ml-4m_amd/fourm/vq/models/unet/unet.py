@@ -8,6 +8,8 @@ upstream checkpoints load with strict=True), same ``forward(sample, timestep, en
 The torch modules below only HOLD the parameters; the forward runs on the HIP kernels (csrc/unet.hip + the NT GEMMs): feature maps as
 (B * H * W, C) bf16 rows, every convolution a GEMM (3 x 3 through fm_unet_im2col), GroupNorm + SiLU in fp32 arithmetic, bf16 GEMM operands
 with fp32 accumulation = upstream's autocast arithmetic.  Inference only (the decoder is trained upstream; no backward here).
+``compute_precision = "fp32"`` (a plain attribute, set after construction like ``FourM.compute_precision``) runs the same launch sequence with
+f32 feature maps and f32 master weights on csrc/unet_f32.hip + fm_gemm_f32: upstream's fp32 evaluation, for verification (_UNetEngineF32).
 Not implemented (rejected loudly): class conditioning, scale-shift norm, ResBlock up / down sampling, the new attention order, dropout."""
 import math
 from typing import Optional, Union
@@ -122,6 +124,9 @@ class PatchedUNetCondCat(nn.Module):
         for p in self.out[2].parameters():
             p.detach().zero_()
         self._engine = None
+        # "bf16" = the hot path (autocast arithmetic); "fp32" = f32 feature maps and weights on the plain kernels of csrc/unet_f32.hip.
+        # Read at every evaluation; the FOURM_PRECISION environment variable is NOT consulted here (it belongs to the trunk).
+        self.compute_precision = "bf16"
 
     @property
     def device(self):
@@ -136,10 +141,16 @@ class PatchedUNetCondCat(nn.Module):
                 cond_mask: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
         """sample (B, C, H, W); timestep: number or (B,) / (1,) tensor; encoder_hidden_states (B, D, Hc, Wc): the de-quantised latents;
         cond_mask (B, Hc, Wc) bool, True = that conditioning vector is zeroed (unet.py:727-729).  Returns f32 (B, out_channels, H, W)."""
+        prec = self.compute_precision
+        if prec not in ("bf16", "fp32"):
+            raise ValueError(f"compute_precision {prec!r}: 'bf16' or 'fp32'")
         if not sample.is_cuda:
             raise RuntimeError("PatchedUNetCondCat runs on the HIP kernels only: move the model and its inputs to an MI355X (there is no CPU path)")
-        if self._engine is None:
-            self._engine = _UNetEngine(self)
+        if self._engine is None or self._engine.precision != prec:
+            # (a new engine: the weight images, scratch and captured graphs of the other precision go with the old one)
+            self._engine = (_UNetEngineF32 if prec == "fp32" else _UNetEngine)(self)
+        if prec == "fp32":                                       # always eager: the verification mode has no use for graph replay
+            return self._engine.forward(sample, timestep, encoder_hidden_states, cond_mask)
         if UNET_GRAPH and not self.training and not torch.cuda.is_current_stream_capturing():
             return self._engine.forward_graphed(sample, timestep, encoder_hidden_states, cond_mask)
         return self._engine.forward(sample, timestep, encoder_hidden_states, cond_mask)
@@ -151,6 +162,7 @@ def unet_patched(**kwargs):
 
 class _UNetEngine:
     """Launch sequence of one UNet evaluation.  bf16 weight images are cached per parameter (refreshed when the parameter changed)."""
+    precision = "bf16"
 
     def __init__(self, net: PatchedUNetCondCat):
         self.net = net
@@ -171,7 +183,7 @@ class _UNetEngine:
     def w_conv(self, conv):
         """(Cout, k * k * Cin padded to 64) bf16: conv.weight with the taps outermost, the GEMM's W operand behind fm_unet_im2col."""
         w = conv.weight
-        key = ("w", id(w))
+        key = ("w", id(w), self.precision)
         hit = self._w.get(key)
         if hit is None or hit[0] != self._stamp(w):
             co = w.shape[0]
@@ -188,7 +200,7 @@ class _UNetEngine:
         """Every ResBlock's emb_layers Linear stacked into one (sum Cout, 4 mc) operand + bias: ONE GEMM per evaluation gives all the
         per-block timestep embeddings (the input silu(emb) is the same for all of them)."""
         ps = [p for m in self._res for p in (m.emb_layers[1].weight, m.emb_layers[1].bias)]
-        key = ("emb_all",)
+        key = ("emb_all", self.precision)
         hit = self._w.get(key)
         if hit is None or hit[0] != self._stamp(*ps):
             te = self._res[0].emb_layers[1].weight.shape[1]
@@ -198,10 +210,13 @@ class _UNetEngine:
             for m, o in zip(self._res, self._emb_off):
                 wf[o:o + m.cout] = m.emb_layers[1].weight.detach()
                 bf[o:o + m.cout] = m.emb_layers[1].bias.detach()
-            img = torch.empty(self._emb_total, te, dtype=torch.bfloat16, device=dev)
-            ops.f32_to_bf16(wf, img)
-            hit = self._w[key] = (self._stamp(*ps), img, bf)
+            hit = self._w[key] = (self._stamp(*ps), self._emb_image(wf), bf)
         return hit[1], hit[2]
+
+    def _emb_image(self, wf):
+        img = torch.empty(wf.shape, dtype=torch.bfloat16, device=wf.device)
+        ops.f32_to_bf16(wf, img)
+        return img
 
     def buf(self, tag, rows, cols, dtype=torch.bfloat16):
         key = (tag, dtype, torch.cuda.current_stream(self.net.device).cuda_stream, ops.SCRATCH_TAG)      # one scratch set per stream / per captured graph
@@ -308,7 +323,7 @@ class _UNetEngine:
         """forward() through a captured graph per (shapes, mask or not, stream).  The first two evaluations of a key run eagerly (they build the
         cached weight images and size every scratch buffer); the third is captured.  A parameter that changed (version / storage) drops the graphs."""
         dev = sample.device
-        key = (tuple(sample.shape), tuple(cond.shape), cond_mask is not None, torch.cuda.current_stream(dev).cuda_stream)
+        key = (self.precision, tuple(sample.shape), tuple(cond.shape), cond_mask is not None, torch.cuda.current_stream(dev).cuda_stream)
         stamp = self._weights_stamp()
         if getattr(self, "_graph_stamp", None) != stamp:
             self._graphs, self._graph_warm, self._graph_stamp = {}, {}, stamp
@@ -419,7 +434,7 @@ class _UNetEngine:
 
     def w_conv_lin(self, lin):
         w = lin.weight
-        key = ("lin", id(w))
+        key = ("lin", id(w), self.precision)
         hit = self._w.get(key)
         if hit is None or hit[0] != self._stamp(w):
             o, i = w.shape
@@ -429,3 +444,153 @@ class _UNetEngine:
             img[:, :i] = tmp
             hit = self._w[key] = (self._stamp(w), img)
         return hit[1]
+
+
+class _UNetEngineF32(_UNetEngine):
+    """The same launch sequence in fp32 (compute_precision = "fp32"): f32 feature maps and scratch, the f32 master weights with the taps outermost
+    (no bf16 image, no padding to 64), csrc/unet_f32.hip for everything that is not a GEMM and fm_gemm_f32 for every convolution and Linear
+    (a 3 x 3 convolution is always fm_unet_im2col_f32 + that GEMM: the implicit-GEMM and split-K paths belong to the bf16 kernels).  Always
+    eager.  Upstream's fp32 evaluation (the UNet outside an autocast context), for verification; not a hot path."""
+    precision = "fp32"
+
+    # ---- cached operands -------------------------------------------------------------------------------------------------------------
+    def w_conv(self, conv):
+        """(Cout, k * k * Cin) f32: conv.weight with the taps outermost, the GEMM's W operand behind fm_unet_im2col_f32."""
+        w = conv.weight
+        key = ("w", id(w), self.precision)
+        hit = self._w.get(key)
+        if hit is None or hit[0] != self._stamp(w):
+            flat = (w.detach().permute(0, 2, 3, 1) if w.dim() == 4 else w.detach().permute(0, 2, 1)).reshape(w.shape[0], -1).float().contiguous()
+            hit = self._w[key] = (self._stamp(w), flat)
+        return hit[1]
+
+    def w_conv_lin(self, lin):
+        return lin.weight.detach().float().contiguous()                  # (the f32 master itself)
+
+    def _emb_image(self, wf):
+        return wf                                                        # (the stacked f32 masters themselves)
+
+    def buf(self, tag, rows, cols, dtype=torch.float32):
+        return super().buf(tag, rows, cols, dtype)
+
+    # ---- building blocks -------------------------------------------------------------------------------------------------------------
+    def gemm(self, x, w, bias, out, M, N, K):
+        ops.gemm_nt(x, w, out, epilogue=L.EPI_F32, bias=bias.detach().float().contiguous() if bias is not None else None, M=M, N=N, K=K)      # f32 operands: fm_gemm_f32
+        return out
+
+    def im2col(self, tag, src1, C1, B, H, W, ksize=3, stride=1, up1=0, src2=None, C2=0, H2=0, W2=0):
+        kp = ksize * ksize * (C1 + C2)
+        pad = ksize // 2
+        Ho, Wo = (H + 2 * pad - ksize) // stride + 1, (W + 2 * pad - ksize) // stride + 1
+        out = self.buf(tag, B * Ho * Wo, kp)
+        L.check(L.unet_im2col_f32(ops._p(src1), src1.stride(0), C1, ops._p(src2), src2.stride(0) if src2 is not None else 0, C2, H2, W2, ops._p(out), kp, kp,
+                                  B, H, W, ksize, stride, up1, ops._stream()))
+        return out, Ho, Wo
+
+    def gn(self, tag, x, norm, B, HW, C, silu, add=None):
+        y = self.buf(tag, B * HW, C)
+        L.check(L.groupnorm_nhwc_f32(ops._p(x), x.stride(0), ops._p(add), add.stride(0) if add is not None else 0, ops._p(norm.weight.detach()),
+                                     ops._p(norm.bias.detach()), ops._p(y), C, B, HW, C, norm.num_groups, float(norm.eps), 1 if silu else 0, ops._stream()))
+        return y
+
+    def add(self, a, b, R, C):
+        out = torch.empty(R, C, dtype=torch.float32, device=a.device)
+        L.check(L.add_f32(ops._p(a), a.stride(0), ops._p(b), b.stride(0), ops._p(out), C, R, C, ops._stream()))
+        return out
+
+    def conv3(self, tag, x, conv, B, H, W, stride=1, up1=0, out=None):
+        C, Co = conv.weight.shape[1], conv.weight.shape[0]
+        col, Ho, Wo = self.im2col("col", x, C, B, H, W, 3, stride, up1)
+        if out is None:
+            out = self.buf(tag, B * Ho * Wo, Co)
+        self.gemm(col, self.w_conv(conv), conv.bias, out, B * Ho * Wo, Co, 9 * C)
+        return out, Ho, Wo
+
+    def res(self, tag, m, x, emb_all, B, H, W):
+        R = B * H * W
+        a = self.gn("act", x, m.in_layers[0], B, H * W, m.cin, True)
+        h, _, _ = self.conv3("h1", a, m.in_layers[2], B, H, W)
+        o = self._emb_off[self._res_index[id(m)]]
+        a2 = self.gn("act", h, m.out_layers[0], B, H * W, m.cout, True, add=emb_all[:, o:o + m.cout])
+        h2, _, _ = self.conv3("h2", a2, m.out_layers[3], B, H, W)
+        xs = x
+        if not isinstance(m.skip_connection, nn.Identity):
+            xs = self.gemm(x, self.w_conv(m.skip_connection), m.skip_connection.bias, self.buf("skipc", R, m.cout), R, m.cout, m.cin)
+        return self.add(xs, h2, R, m.cout)
+
+    def attn(self, m, x, B, H, W):
+        T, C = H * W, m.ch
+        n = self.gn("act", x, m.norm, B, T, C, False)
+        qkv = self.gemm(n, self.w_conv(m.qkv), m.qkv.bias, self.buf("qkv", B * T, 3 * C), B * T, 3 * C, C)
+        a = self.buf("attn_o", B * T, C)
+        L.check(L.unet_attention_f32(ops._p(qkv), 3 * C, ops._p(a), C, B, T, m.heads, C // m.heads, ops._stream()))
+        pr = self.gemm(a, self.w_conv(m.proj_out), m.proj_out.bias, self.buf("h2", B * T, C), B * T, C, C)
+        return self.add(x, pr, B * T, C)
+
+    # ---- one evaluation --------------------------------------------------------------------------------------------------------------
+    def forward(self, sample, timestep, cond, cond_mask):
+        net = self.net
+        dev = sample.device
+        f32 = torch.float32
+        B, C, H, W = sample.shape
+        P = net.P_H
+        if H % P or W % P:
+            raise ValueError(f"Image sizes {H}x{W} must be divisible by patch sizes {P}x{P}")
+        nh, nw = H // P, W // P
+        CP = C * P * P
+        if CP % 4 or net.cond_channels % 4:
+            raise NotImplementedError("patch / conditioning widths must be multiples of 4 (compute_precision = 'fp32')")
+        if nh != nw or H != W:
+            raise NotImplementedError("non-square inputs")
+        R = B * nh * nw
+        # 'b c (nh ph) (nw pw) -> (b nh nw) (c ph pw)': the rows fm_vq_patchify writes, in f32 (plumbing)
+        rows = self.buf("patch", R, CP)
+        rows.view(B, nh, nw, C, P, P).copy_(sample.detach().to(f32).contiguous().view(B, C, nh, P, nw, P).permute(0, 2, 4, 1, 3, 5))
+        cnd = cond.detach().to(f32)
+        if cond_mask is not None:
+            cnd = torch.where(cond_mask[:, None].to(dev), torch.zeros((), device=dev), cnd)
+        D, Hc, Wc = cnd.shape[1:]
+        crow = cnd.permute(0, 2, 3, 1).reshape(B * Hc * Wc, D).contiguous()
+        # timestep embedding -> time_embed MLP -> silu -> every ResBlock's projection in one GEMM
+        t = torch.as_tensor(timestep, device=dev).reshape(-1).to(f32)
+        if t.numel() == 1:
+            t = t.expand(B)
+        t = t.contiguous()
+        mc, te = net.model_channels, net.model_channels * 4
+        temb = self.buf("temb", B, mc)
+        L.check(L.timestep_embedding_f32(ops._p(t), ops._p(temb), mc, B, mc, 10000.0, ops._stream()))
+        l0, l2 = net.time_embed[0], net.time_embed[2]
+        e1 = self.gemm(temb, self.w_conv_lin(l0), l0.bias, self.buf("e1", B, te), B, te, mc)
+        s1 = self.buf("s1", B, te)
+        L.check(L.silu_f32(ops._p(e1), ops._p(s1), B * te, ops._stream()))
+        e2 = self.gemm(s1, self.w_conv_lin(l2), l2.bias, self.buf("e2", B, te), B, te, te)
+        s2 = self.buf("s2", B, te)
+        L.check(L.silu_f32(ops._p(e2), ops._p(s2), B * te, ops._stream()))
+        wall, ball = self.w_emb_all()
+        emb_all = self.gemm(s2, wall, ball, self.buf("emb_all", B, self._emb_total), B, self._emb_total, te)
+        # input blocks
+        first = net.input_blocks[0][0]
+        col, _, _ = self.im2col("col", rows, CP, B, nh, nw, 3, 1, 0, src2=crow, C2=D, H2=Hc, W2=Wc)
+        ch0 = first.weight.shape[0]
+        h = self.gemm(col, self.w_conv(first), first.bias, torch.empty(R, ch0, dtype=f32, device=dev), R, ch0, col.shape[1])
+        hs, hh, ww = [(h, nh, nw)], nh, nw
+        for blk in list(net.input_blocks)[1:]:
+            h, hh, ww = self.run(blk, h, emb_all, B, hh, ww)
+            hs.append((h, hh, ww))
+        h, hh, ww = self.run(net.middle_block, h, emb_all, B, hh, ww)
+        for blk in net.output_blocks:
+            skip, sh, sw = hs.pop()
+            assert (sh, sw) == (hh, ww)
+            C1, C2 = h.shape[1], skip.shape[1]
+            cat = torch.empty(B * hh * ww, C1 + C2, dtype=f32, device=dev)
+            L.check(L.unet_im2col_f32(ops._p(h), h.stride(0), C1, ops._p(skip), skip.stride(0), C2, hh, ww, ops._p(cat), C1 + C2, C1 + C2, B, hh, ww, 1, 1, 0,
+                                      ops._stream()))
+            h, hh, ww = self.run(blk, cat, emb_all, B, hh, ww)
+        a = self.gn("act", h, net.out[0], B, hh * ww, h.shape[1], True)
+        conv = net.out[2]
+        OP = conv.weight.shape[0]
+        y = self.buf("y", B * hh * ww, ru(OP, 4))
+        self.conv3("y", a, conv, B, hh, ww, out=y)
+        img = torch.empty(B, net.out_channels, H, W, dtype=f32, device=dev)
+        L.check(L.vq_unpatchify(ops._p(y), y.stride(0), ops._p(img), B, net.out_channels, H, W, P, ops._stream()))
+        return img

@@ -9,7 +9,10 @@ hand-written, fourm/vq/engine.py), and ``DiVAE`` (:498-764): the conditional-UNe
 Precision = upstream's autocast arithmetic: the 12 ViT blocks with bf16 GEMM operands (fp32 accumulate, fp32 residual /
 LayerNorm / softmax); the tanh post-MLP, the 1x1 projection and the codebook search in exact fp32 (upstream disables
 autocast there, vit_models.py:494-496, quantize_lucid.py:388-390).  Code assignment given identical latents is bit-identical
-(tests); end-to-end token agreement against the all-fp32 upstream run is measured and asserted by the tests."""
+(tests); end-to-end token agreement against the all-fp32 upstream run is measured and asserted by the tests.
+``model.compute_precision = "fp32"`` (``VQ`` and ``DiVAE``; assigned after construction) runs the ViT encoder, the projection, the code search,
+the conditional UNet and the sampling pipeline entirely in fp32 - upstream's run without autocast - on the trunk's fp32 kernels,
+csrc/unet_f32.hip and fm_gemm_f32; ``VQVAE``, the MLP / Memcodes tokenizers and training mode refuse it (NotImplementedError)."""
 import copy
 from typing import Any, Dict, List, Optional, Tuple, Union
 
@@ -86,6 +89,38 @@ class VQ(nn.Module, PyTorchModelHubMixin):
                     for p in mod.parameters():
                         p.requires_grad = False
 
+    # ---- compute precision ---------------------------------------------------------------------------------------------------------
+    @property
+    def compute_precision(self) -> str:
+        """"bf16" (default): upstream's autocast arithmetic on the hot-path kernels.  "fp32": everything a ``DiVAE`` touches - ViT encoder,
+        projection, code search, conditional UNet, sampling pipeline - in fp32 (trunk fp32 kernels, csrc/unet_f32.hip, fm_gemm_f32): upstream's
+        run without autocast, for verification and for reproducing its token files.  Assign after construction, like ``FourM.compute_precision``.
+        Refused (NotImplementedError) where a part has no fp32 form: the ViT decoder of ``VQVAE``, the MLP / Memcodes tokenizers, training mode."""
+        return self.__dict__.get("_compute_precision", "bf16")
+
+    @compute_precision.setter
+    def compute_precision(self, value: str):
+        if value not in ("bf16", "fp32"):
+            raise ValueError(f"compute_precision {value!r}: 'bf16' or 'fp32'")
+        if value == "fp32":
+            why = self._fp32_unsupported()
+            if why is not None:
+                raise NotImplementedError(f"compute_precision = 'fp32': {why}")
+        self.__dict__["_compute_precision"] = value
+        self.encoder.compute_precision = value
+        if isinstance(self, DiVAE):
+            self.decoder.compute_precision = value
+
+    def _fp32_unsupported(self):
+        """Why this model cannot run in fp32 mode (None: it can).  Never a silent mix of precisions."""
+        if self._is_mlp():
+            return (f"the MLP tokenizers ({self.enc_type} with the memcodes quantizer) have no precision switch (their path is exact fp32 "
+                    "already where it matters; the switch is built for the ViT tokenizer and the DiVAE decoder)")
+        if isinstance(self, VQVAE):
+            return ("the ViT decoder of VQVAE (decoder blocks, out_proj, out_conv) has no fp32 form; the switch is built for VQ (tokenizer only) "
+                    "and DiVAE (diffusion decoder)")
+        return None
+
     def init_from_ckpt(self, path: str, ignore_keys: List[str] = list()) -> "VQ":
         ckpt = torch.load(path, map_location="cpu", weights_only=False)
         sd = ckpt["model"] if "model" in ckpt else ckpt["state_dict"]
@@ -109,6 +144,7 @@ class VQ(nn.Module, PyTorchModelHubMixin):
             dev = self.quant_proj.weight.device
             mean, std = torch.tensor((0.485, 0.456, 0.406), device=dev), torch.tensor((0.229, 0.224, 0.225), device=dev)
             prep["scale"], prep["shift"] = (2.0 * std).contiguous(), (2.0 * mean - 1.0).contiguous()
+            prep["mean_std"] = ((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))      # (fp32 mode evaluates upstream's own expression, 2 * denormalize(x) - 1)
         return prep
 
     def to_rgb(self, x: torch.Tensor) -> torch.Tensor:
@@ -143,6 +179,8 @@ class VQ(nn.Module, PyTorchModelHubMixin):
         from .engine import vq_encode
         if self.training and self.quantize.training and self._inference_only():
             raise NotImplementedError(f"training-mode quantizer (EMA codebook update): {self._inference_only()}; call .eval()")
+        if self.compute_precision == "fp32" and self.training and self.quantize.training:
+            raise NotImplementedError("compute_precision = 'fp32' is inference only (no EMA codebook update / training forward in fp32): call .eval()")
         quant, loss, tokens = vq_encode(self, self.prepare_input(x))
         if self.training and self.quantize.training:
             # upstream's training-mode quantizer: EMA codebook update + the commitment term's VALUE (quantize_lucid.py:409-426, :540-548)
