@@ -519,6 +519,26 @@ int fm_add_f32(const void* a, int lda, const void* b, int ldb, void* out, int ld
 int fm_silu_f32(const void* x, void* y, int64_t n, void* stream);                                                        /* y = x * sigmoid(x), f32 to f32 */
 /* out[b] = [cos(t_b f_i) | sin(t_b f_i)], f_i = exp(-ln(max_period) i / (dim / 2)); t f32 (B), out f32 (B, ldo)   (nn.py:120-140) */
 int fm_timestep_embedding_f32(const void* t, void* out, int ldo, int B, int dim, float max_period, void* stream);
+/* Backward of this mode (csrc/unet_f32_bwd.hip): what training the UNet on a frozen encoder needs besides fm_gemm_f32 (dX = dY W and dW = dY^T X
+ * through its strides).  Fixed summation orders, no atomics, every output element written once: two runs agree bit for bit.
+ * fm_unet_col2im_f32: the adjoint of fm_unet_im2col_f32 with respect to src1 for ksize 3 (C2 = 0), stride 1 | 2, up1 0 | 1, (H, W) the forward's
+ *   logical grid: dsrc[(b, sy, sx)][c] (+)= sum of the col entries the forward filled from that pixel, taps in a fixed order (<= 9, <= 36 with up1).
+ *   col f32 (B * Ho * Wo, ldc >= 9 C); dsrc f32 (B * (H >> up1) * (W >> up1), ld >= C); accumulate = 1 adds to dsrc; nothing is written outside
+ *   columns [0, C).  C, ld, ldc multiples of 4, 16-byte aligned pointers. */
+int fm_unet_col2im_f32(const void* col, int ldc, void* dsrc, int ld, int C, int B, int H, int W, int ksize, int stride, int up1, int accumulate, void* stream);
+/* Backward of fm_groupnorm_nhwc_f32: the two-pass statistics of x + add[b][c] are recomputed as the forward computes them, with silu the
+ * pre-activation is rebuilt and silu' applied.  dx f32 (B * HW, lddx); dadd[b][c] = sum_HW dx (f32 (B, ld_dadd), or NULL); dw[c], db[c] (f32 (C),
+ * either may be NULL) are OVERWRITTEN with the sums over (B, HW): per-sample partial sums in scratch (2 * B * C floats; NULL allowed when dw and
+ * db are), combined over the samples in order.  Same shape contract as the forward. */
+int fm_groupnorm_nhwc_bwd_f32(const void* dy, int lddy, const void* x, int ldx, const void* add, int ld_add, const void* w, const void* b, void* dx, int lddx,
+                              void* dw, void* db, void* dadd, int ld_dadd, void* scratch, int B, int HW, int C, int groups, float eps, int silu, void* stream);
+/* Backward of fm_unet_attention_f32: the probabilities are recomputed from qkv with the forward's arithmetic; dout f32 (B * T, lddo) is the
+ * gradient of its output, dqkv f32 (B * T, lddqkv) receives [dq | dk | dv] per head, every element written exactly once (one workgroup per
+ * query writes dq, one per key dk and dv).  scratch: 3 * B * heads * T floats (row max, row sum, sum_s P dP).  The forward's limits; lddo % 4 == 0
+ * and a 16-byte aligned dout as well. */
+int fm_unet_attention_bwd_f32(const void* qkv, int ld, const void* dout, int lddo, void* dqkv, int lddqkv, void* scratch, int B, int T, int heads, int ch,
+                              void* stream);
+int fm_silu_bwd_f32(const void* dy, const void* x, void* dx, int64_t n, void* stream);      /* dx = dy s (1 + x (1 - s)), s = sigmoid(x), n contiguous f32 */
 
 /* ------------------------------------------------------------------------------------------------
  * VQ tokenizer front end (fourm/vq/vqvae.py:302-331)

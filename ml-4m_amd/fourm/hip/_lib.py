@@ -252,6 +252,11 @@ unet_attention_f32 = _sig("fm_unet_attention_f32", vp, i32, vp, i32, i32, i32, i
 add_f32 = _sig("fm_add_f32", vp, i32, vp, i32, vp, i32, i64, i32, vp)
 silu_f32 = _sig("fm_silu_f32", vp, vp, i64, vp)
 timestep_embedding_f32 = _sig("fm_timestep_embedding_f32", vp, vp, i32, i32, i32, f32, vp)
+# ... and its backward (csrc/unet_f32_bwd.hip)
+unet_col2im_f32 = _sig("fm_unet_col2im_f32", vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp)
+groupnorm_nhwc_bwd_f32 = _sig("fm_groupnorm_nhwc_bwd_f32", vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, i32, f32, i32, vp)
+unet_attention_bwd_f32 = _sig("fm_unet_attention_bwd_f32", vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, vp)
+silu_bwd_f32 = _sig("fm_silu_bwd_f32", vp, vp, vp, i64, vp)
 diffusion_x0 = _sig("fm_diffusion_x0", vp, vp, f32, f32, vp, i64, vp)
 quantile_abs = _sig("fm_quantile_abs", vp, i32, i64, f32, vp, vp)
 diffusion_step = _sig("fm_diffusion_step", vp, vp, f32, f32, vp, vp, vp, f32, f32, f32, f32, vp, vp, i32, i64, vp)
@@ -269,7 +274,8 @@ EXPORTS = ["fm_attn_decode", "fm_vit_patch_rows", "fm_vit_emb_rows", "fm_vit_col
            "fm_sumsq", "fm_clip_coef", "fm_vq_patchify", "fm_l2norm_rows", "fm_vq_assign",
            "fm_sample_tokens", "fm_maskgit_commit", "fm_gemm_f32", "fm_attn_f32_fwd", "fm_attn_f32_bwd", "fm_layernorm_bwd_f32", "fm_headnorm_f32_fwd", "fm_headnorm_f32_bwd",
            "fm_swiglu_bwd_f32", "fm_gelu_bwd_f32", "fm_colsum_f32", "fm_cross_entropy_f32", "fm_lab_set",
-           "fm_unet_im2col_f32", "fm_groupnorm_nhwc_f32", "fm_unet_attention_f32", "fm_add_f32", "fm_silu_f32", "fm_timestep_embedding_f32"]
+           "fm_unet_im2col_f32", "fm_groupnorm_nhwc_f32", "fm_unet_attention_f32", "fm_add_f32", "fm_silu_f32", "fm_timestep_embedding_f32",
+           "fm_unet_col2im_f32", "fm_groupnorm_nhwc_bwd_f32", "fm_unet_attention_bwd_f32", "fm_silu_bwd_f32"]
 
 
 def check(rc: int):

@@ -7,9 +7,12 @@ upstream checkpoints load with strict=True), same ``forward(sample, timestep, en
 
 The torch modules below only HOLD the parameters; the forward runs on the HIP kernels (csrc/unet.hip + the NT GEMMs): feature maps as
 (B * H * W, C) bf16 rows, every convolution a GEMM (3 x 3 through fm_unet_im2col), GroupNorm + SiLU in fp32 arithmetic, bf16 GEMM operands
-with fp32 accumulation = upstream's autocast arithmetic.  Inference only (the decoder is trained upstream; no backward here).
+with fp32 accumulation = upstream's autocast arithmetic.  The bf16 path is inference only (no bf16 backward).
 ``compute_precision = "fp32"`` (a plain attribute, set after construction like ``FourM.compute_precision``) runs the same launch sequence with
 f32 feature maps and f32 master weights on csrc/unet_f32.hip + fm_gemm_f32: upstream's fp32 evaluation, for verification (_UNetEngineF32).
+In that mode, in training mode with gradients enabled and a trainable parameter, the evaluation is differentiable with respect to the
+PARAMETERS (_UNetTrainF32 on csrc/unet_f32_bwd.hip: the decoder trained on a frozen encoder).  The verification-mode backward: no throughput
+claim, no gradient to the sample or the conditioning, square inputs only, not graph-capturable.
 Not implemented (rejected loudly): class conditioning, scale-shift norm, ResBlock up / down sampling, the new attention order, dropout."""
 import math
 from typing import Optional, Union
@@ -124,6 +127,7 @@ class PatchedUNetCondCat(nn.Module):
         for p in self.out[2].parameters():
             p.detach().zero_()
         self._engine = None
+        self._train_engine = None                       # _UNetTrainF32, built at the first differentiable evaluation
         # "bf16" = the hot path (autocast arithmetic); "fp32" = f32 feature maps and weights on the plain kernels of csrc/unet_f32.hip.
         # Read at every evaluation; the FOURM_PRECISION environment variable is NOT consulted here (it belongs to the trunk).
         self.compute_precision = "bf16"
@@ -136,16 +140,33 @@ class PatchedUNetCondCat(nn.Module):
     def dtype(self):
         return next(self.parameters()).dtype
 
-    @torch.no_grad()
     def forward(self, sample: torch.Tensor, timestep: Union[torch.Tensor, float, int], encoder_hidden_states: torch.Tensor = None,
                 cond_mask: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
         """sample (B, C, H, W); timestep: number or (B,) / (1,) tensor; encoder_hidden_states (B, D, Hc, Wc): the de-quantised latents;
-        cond_mask (B, Hc, Wc) bool, True = that conditioning vector is zeroed (unet.py:727-729).  Returns f32 (B, out_channels, H, W)."""
+        cond_mask (B, Hc, Wc) bool, True = that conditioning vector is zeroed (unet.py:727-729).  Returns f32 (B, out_channels, H, W).
+
+        With ``compute_precision == "fp32"``, in training mode, with gradients enabled and at least one parameter that requires a gradient, the
+        result carries a ``grad_fn``: its backward adds the gradient of every trainable parameter to ``.grad`` (torch semantics) on the kernels of
+        csrc/unet_f32_bwd.hip.  The values are bit-identical to the eval-mode fp32 evaluation.  Scope: the decoder on a frozen encoder - the inputs
+        get no gradient (a sample or conditioning that requires one is refused), no bf16 backward, square inputs, no graph capture.  Every other
+        combination evaluates without a gradient path, as before."""
         prec = self.compute_precision
         if prec not in ("bf16", "fp32"):
             raise ValueError(f"compute_precision {prec!r}: 'bf16' or 'fp32'")
         if not sample.is_cuda:
             raise RuntimeError("PatchedUNetCondCat runs on the HIP kernels only: move the model and its inputs to an MI355X (there is no CPU path)")
+        if prec == "fp32" and self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            if sample.requires_grad or (torch.is_tensor(encoder_hidden_states) and encoder_hidden_states.requires_grad):
+                raise NotImplementedError("PatchedUNetCondCat: the backward is built for the frozen-encoder scope (parameter gradients only): the sample "
+                                          "and the conditioning get no gradient - detach them")
+            if self._train_engine is None:
+                self._train_engine = _UNetTrainF32(self)
+            anchor = next(p for p in self.parameters() if p.requires_grad)
+            return _UNetTrainStep.apply(anchor, self._train_engine, sample, timestep, encoder_hidden_states, cond_mask)
+        with torch.no_grad():
+            return self._evaluate(prec, sample, timestep, encoder_hidden_states, cond_mask)
+
+    def _evaluate(self, prec, sample, timestep, encoder_hidden_states, cond_mask):
         if self._engine is None or self._engine.precision != prec:
             # (a new engine: the weight images, scratch and captured graphs of the other precision go with the old one)
             self._engine = (_UNetEngineF32 if prec == "fp32" else _UNetEngine)(self)
@@ -594,3 +615,288 @@ class _UNetEngineF32(_UNetEngine):
         img = torch.empty(B, net.out_channels, H, W, dtype=f32, device=dev)
         L.check(L.vq_unpatchify(ops._p(y), y.stride(0), ops._p(img), B, net.out_channels, H, W, P, ops._stream()))
         return img
+
+
+class _UNetTrainF32(_UNetEngineF32):
+    """Training form of the fp32 launch sequence: the forward of _UNetEngineF32 launch for launch (bit-identical values), with everything the
+    backward reads - the inputs of the convolutions, GroupNorms and Linears, qkv - in tensors owned by that call; the shared ``buf(tag)``
+    scratch only holds what one launch hands to the next (the column matrices, re-made by fm_unet_im2col_f32 in the backward).  forward_train
+    returns the image and the closure that walks the tape in reverse: out, output_blocks, middle_block, input_blocks, the time-embedding MLP.
+    Parameter gradients only (the decoder on a frozen encoder): the first convolution computes its dW alone.  Every reduction of the backward
+    runs in a fixed order (csrc/unet_f32_bwd.hip, fm_gemm_f32, fm_vit_colsum): two runs give the same bits.  Verification mode, not a hot path."""
+
+    def new(self, rows, cols):
+        return torch.empty(rows, cols, dtype=torch.float32, device=self.net.device)
+
+    def _colsum_ws(self, N):
+        ws = getattr(self, "_ws64", None)
+        if ws is None or ws.numel() < 64 * N or ws.device != self.net.device:
+            ws = self._ws64 = torch.empty(64 * N, dtype=torch.float64, device=self.net.device)
+        return ws
+
+    # ---- parameter gradients: torch semantics (added to .grad, created when None, in the parameter's own layout) -------------------------
+    @staticmethod
+    def _acc(p, g):
+        g = g.reshape(p.shape).to(p.dtype)
+        if p.grad is None:
+            p.grad = g.clone(memory_format=torch.contiguous_format)
+        else:
+            p.grad.add_(g)
+
+    def _wgrad(self, dout, xmat, weight, bias, M, N, K, to_param=None):
+        """dW = dout^T xmat (N, K) and db = column sums of dout, for the operands that require a gradient (xmat: a callable that makes the matrix)."""
+        if weight.requires_grad:
+            dw = torch.zeros(N, K, dtype=torch.float32, device=dout.device)
+            ops.gemm_tn(dout, xmat(), dw, N=N, K=K, R=M)
+            self._acc(weight, to_param(dw) if to_param is not None else dw)
+        if bias is not None and bias.requires_grad:
+            db = torch.zeros(N, dtype=torch.float32, device=dout.device)
+            ops.vit_colsum(dout, db, self._colsum_ws(N), R=M)
+            self._acc(bias, db)
+
+    def _dx(self, dout, wimg, out, M, N, K):
+        """out (M, K) = dout (M, N) wimg (N, K): fm_gemm_f32 with the weight image read through its strides"""
+        return ops._gemm_f32(dout, wimg.t(), out, epilogue=L.EPI_F32, M=M, N=K, K=N)
+
+    # ---- building blocks: each returns (output, backward closure dout -> dx) -------------------------------------------------------------
+    def lin_t(self, x, mod, wimg, M, N, K, need_dx=True):
+        out = self.gemm(x, wimg, mod.bias, self.new(M, N), M, N, K)
+
+        def bwd(dout):
+            self._wgrad(dout, lambda: x, mod.weight, mod.bias, M, N, K)
+            return self._dx(dout, wimg, self.new(M, K), M, N, K) if need_dx else None
+        return out, bwd
+
+    def conv3_t(self, x, conv, B, H, W, stride=1, up1=0, need_dx=True, src2=None):
+        """3 x 3 convolution; src2 = (rows, C2, H2, W2): the conditioning of the first convolution (no gradient to either source then)"""
+        C, Co = conv.weight.shape[1], conv.weight.shape[0]
+        C1 = C - (src2[1] if src2 else 0)
+        two = dict(src2=src2[0], C2=src2[1], H2=src2[2], W2=src2[3]) if src2 else {}
+        col, Ho, Wo = self.im2col("col", x, C1, B, H, W, 3, stride, up1, **two)
+        M = B * Ho * Wo
+        wimg = self.w_conv(conv)
+        out = self.gemm(col, wimg, conv.bias, self.new(M, ru(Co, 4)), M, Co, 9 * C)
+
+        def bwd(dout):
+            self._wgrad(dout, lambda: self.im2col("col", x, C1, B, H, W, 3, stride, up1, **two)[0], conv.weight, conv.bias, M, Co, 9 * C,
+                        lambda dw: dw.view(Co, 3, 3, C).permute(0, 3, 1, 2))          # taps outermost -> (Cout, Cin, 3, 3)
+            if not need_dx:
+                return None
+            dcol = self._dx(dout, wimg, self.buf("dcol", M, 9 * C), M, Co, 9 * C)
+            dx = self.new(x.shape[0], C)
+            L.check(L.unet_col2im_f32(ops._p(dcol), 9 * C, ops._p(dx), C, C, B, H, W, 3, stride, up1, 0, ops._stream()))
+            return dx
+        return out, Ho, Wo, bwd
+
+    def gn_t(self, x, norm, B, HW, C, silu, add=None, emb_off=None, S=None):
+        y = self.new(B * HW, C)
+        L.check(L.groupnorm_nhwc_f32(ops._p(x), x.stride(0), ops._p(add), add.stride(0) if add is not None else 0, ops._p(norm.weight.detach()),
+                                     ops._p(norm.bias.detach()), ops._p(y), C, B, HW, C, norm.num_groups, float(norm.eps), 1 if silu else 0, ops._stream()))
+
+        def bwd(dy):
+            dx = self.new(B * HW, C)
+            dev = dy.device
+            dw = torch.empty(C, dtype=torch.float32, device=dev) if norm.weight.requires_grad else None
+            db = torch.empty(C, dtype=torch.float32, device=dev) if norm.bias.requires_grad else None
+            dadd = S["demb"][:, emb_off:emb_off + C] if add is not None else None
+            scratch = self.buf("gn_bwd", 2 * B, C) if dw is not None or db is not None else None
+            L.check(L.groupnorm_nhwc_bwd_f32(ops._p(dy), dy.stride(0), ops._p(x), x.stride(0), ops._p(add), add.stride(0) if add is not None else 0,
+                                             ops._p(norm.weight.detach()), ops._p(norm.bias.detach()), ops._p(dx), C, ops._p(dw), ops._p(db), ops._p(dadd),
+                                             dadd.stride(0) if dadd is not None else 0, ops._p(scratch), B, HW, C, norm.num_groups, float(norm.eps),
+                                             1 if silu else 0, ops._stream()))
+            if dw is not None:
+                self._acc(norm.weight, dw)
+            if db is not None:
+                self._acc(norm.bias, db)
+            return dx
+        return y, bwd
+
+    def res_t(self, m, x, emb_all, B, H, W, S):
+        R = B * H * W
+        a, b_gn1 = self.gn_t(x, m.in_layers[0], B, H * W, m.cin, True)
+        h, _, _, b_c1 = self.conv3_t(a, m.in_layers[2], B, H, W)
+        o = self._emb_off[self._res_index[id(m)]]
+        a2, b_gn2 = self.gn_t(h, m.out_layers[0], B, H * W, m.cout, True, add=emb_all[:, o:o + m.cout], emb_off=o, S=S)
+        h2, _, _, b_c2 = self.conv3_t(a2, m.out_layers[3], B, H, W)
+        xs, b_skip = x, None
+        if not isinstance(m.skip_connection, nn.Identity):
+            xs, b_skip = self.lin_t(x, m.skip_connection, self.w_conv(m.skip_connection), R, m.cout, m.cin)
+        out = self.add(xs, h2, R, m.cout)
+
+        def bwd(dout):                     # the gradient of x: through the GroupNorm branch and through the skip path
+            dx = b_gn1(b_c1(b_gn2(b_c2(dout))))
+            return self.add(dx, dout if b_skip is None else b_skip(dout), R, m.cin)
+        return out, bwd
+
+    def attn_t(self, m, x, B, H, W):
+        T, C = H * W, m.ch
+        n, b_gn = self.gn_t(x, m.norm, B, T, C, False)
+        qkv, b_qkv = self.lin_t(n, m.qkv, self.w_conv(m.qkv), B * T, 3 * C, C)
+        a = self.new(B * T, C)
+        L.check(L.unet_attention_f32(ops._p(qkv), 3 * C, ops._p(a), C, B, T, m.heads, C // m.heads, ops._stream()))
+        pr, b_proj = self.lin_t(a, m.proj_out, self.w_conv(m.proj_out), B * T, C, C)
+        out = self.add(x, pr, B * T, C)
+
+        def bwd(dout):
+            da = b_proj(dout)
+            dqkv = self.new(B * T, 3 * C)
+            L.check(L.unet_attention_bwd_f32(ops._p(qkv), 3 * C, ops._p(da), C, ops._p(dqkv), 3 * C, ops._p(self.buf("attn_bwd", B * m.heads * T, 3)),
+                                             B, T, m.heads, C // m.heads, ops._stream()))
+            return self.add(b_gn(b_qkv(dqkv)), dout, B * T, C)
+        return out, bwd
+
+    def run_t(self, seq, h, emb_all, B, H, W, S):
+        bwds = []
+        for m in seq:
+            if isinstance(m, _Res):
+                h, b = self.res_t(m, h, emb_all, B, H, W, S)
+            elif isinstance(m, _Attn):
+                h, b = self.attn_t(m, h, B, H, W)
+            elif isinstance(m, _Down):
+                h, H, W, b = self.conv3_t(h, m.op, B, H, W, stride=2)
+            elif isinstance(m, _Up):
+                h, H, W, b = self.conv3_t(h, m.conv, B, 2 * H, 2 * W, up1=1)
+            else:
+                raise TypeError(type(m))
+            bwds.append(b)
+
+        def bwd(d):
+            for b in reversed(bwds):
+                d = b(d)
+            return d
+        return h, H, W, bwd
+
+    def silu_bwd(self, dy, x):
+        dx = torch.empty_like(x)
+        L.check(L.silu_bwd_f32(ops._p(dy), ops._p(x), ops._p(dx), x.numel(), ops._stream()))
+        return dx
+
+    # ---- one differentiable evaluation ---------------------------------------------------------------------------------------------------
+    def forward_train(self, sample, timestep, cond, cond_mask):
+        """(image, backward): backward(d image) adds every trainable parameter's gradient to its .grad."""
+        net = self.net
+        dev = sample.device
+        f32 = torch.float32
+        if torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError("the training step of the fp32 UNet is not graph-capturable")
+        B, C, H, W = sample.shape
+        P = net.P_H
+        if H % P or W % P:
+            raise ValueError(f"Image sizes {H}x{W} must be divisible by patch sizes {P}x{P}")
+        nh, nw = H // P, W // P
+        CP = C * P * P
+        if CP % 4 or net.cond_channels % 4:
+            raise NotImplementedError("patch / conditioning widths must be multiples of 4 (compute_precision = 'fp32')")
+        if nh != nw or H != W:
+            raise NotImplementedError("non-square inputs")
+        R = B * nh * nw
+        S = {}                                                    # state of THIS call's backward (the gradient of emb_all)
+        stamp = self._weights_stamp()
+        rows = self.new(R, CP)
+        rows.view(B, nh, nw, C, P, P).copy_(sample.detach().to(f32).contiguous().view(B, C, nh, P, nw, P).permute(0, 2, 4, 1, 3, 5))
+        cnd = cond.detach().to(f32)
+        if cond_mask is not None:
+            cnd = torch.where(cond_mask[:, None].to(dev), torch.zeros((), device=dev), cnd)
+        D, Hc, Wc = cnd.shape[1:]
+        crow = cnd.permute(0, 2, 3, 1).reshape(B * Hc * Wc, D).contiguous()
+        t = torch.as_tensor(timestep, device=dev).reshape(-1).to(f32)
+        if t.numel() == 1:
+            t = t.expand(B)
+        t = t.contiguous()
+        mc, te = net.model_channels, net.model_channels * 4
+        temb = self.new(B, mc)
+        L.check(L.timestep_embedding_f32(ops._p(t), ops._p(temb), mc, B, mc, 10000.0, ops._stream()))
+        l0, l2 = net.time_embed[0], net.time_embed[2]
+        w0, w2 = self.w_conv_lin(l0), self.w_conv_lin(l2)
+        e1 = self.gemm(temb, w0, l0.bias, self.new(B, te), B, te, mc)
+        s1 = self.new(B, te)
+        L.check(L.silu_f32(ops._p(e1), ops._p(s1), B * te, ops._stream()))
+        e2 = self.gemm(s1, w2, l2.bias, self.new(B, te), B, te, te)
+        s2 = self.new(B, te)
+        L.check(L.silu_f32(ops._p(e2), ops._p(s2), B * te, ops._stream()))
+        wall, ball = self.w_emb_all()
+        ET = self._emb_total
+        emb_all = self.gemm(s2, wall, ball, self.new(B, ET), B, ET, te)
+        # input blocks
+        first = net.input_blocks[0][0]
+        h, _, _, b_first = self.conv3_t(rows, first, B, nh, nw, need_dx=False, src2=(crow, D, Hc, Wc))
+        hs, hh, ww, b_in = [(h, nh, nw)], nh, nw, []
+        for blk in list(net.input_blocks)[1:]:
+            h, hh, ww, b = self.run_t(blk, h, emb_all, B, hh, ww, S)
+            hs.append((h, hh, ww))
+            b_in.append(b)
+        h, hh, ww, b_mid = self.run_t(net.middle_block, h, emb_all, B, hh, ww, S)
+        b_out = []
+        for blk in net.output_blocks:
+            skip, sh, sw = hs.pop()
+            assert (sh, sw) == (hh, ww)
+            C1, C2 = h.shape[1], skip.shape[1]
+            cat = self.new(B * hh * ww, C1 + C2)
+            L.check(L.unet_im2col_f32(ops._p(h), h.stride(0), C1, ops._p(skip), skip.stride(0), C2, hh, ww, ops._p(cat), C1 + C2, C1 + C2, B, hh, ww, 1, 1, 0,
+                                      ops._stream()))
+            h, hh, ww, b = self.run_t(blk, cat, emb_all, B, hh, ww, S)
+            b_out.append((b, C1))
+        Cl = h.shape[1]
+        a, b_gn = self.gn_t(h, net.out[0], B, hh * ww, Cl, True)
+        conv = net.out[2]
+        OP = conv.weight.shape[0]
+        y, _, _, b_conv = self.conv3_t(a, conv, B, hh, ww)
+        img = torch.empty(B, net.out_channels, H, W, dtype=f32, device=dev)
+        L.check(L.vq_unpatchify(ops._p(y), y.stride(0), ops._p(img), B, net.out_channels, H, W, P, ops._stream()))
+        res = self._res
+
+        def backward(dimg):
+            if self._weights_stamp() != stamp:
+                raise RuntimeError("PatchedUNetCondCat: a parameter was modified between this evaluation and its backward")
+            S["demb"] = torch.zeros(B, ET, dtype=f32, device=dev)
+            # the adjoint of the un-patchify: 'b c (nh ph) (nw pw) -> (b nh nw) (c ph pw)' (plumbing, as in the forward)
+            dy = dimg.detach().to(f32).contiguous().view(B, net.out_channels, nh, P, nw, P).permute(0, 2, 4, 1, 3, 5).reshape(R, OP).contiguous()
+            d = b_gn(b_conv(dy))
+            dskips = []                                           # the skip concatenation's adjoint: a column split, by views
+            for b, C1 in reversed(b_out):
+                dcat = b(d)
+                d = dcat[:, :C1]
+                dskips.append(dcat[:, C1:])                        # (in the order hs was filled)
+            d = b_mid(d)
+            for i in range(len(b_in), 0, -1):                      # hs[i] fed the next block and its skip concatenation
+                d = b_in[i - 1](self.add(d, dskips[i], d.shape[0], d.shape[1]))
+            b_first(self.add(d, dskips[0], d.shape[0], d.shape[1]))
+            # the per-ResBlock slices of emb_all -> the stacked projection -> time_embed
+            demb = S.pop("demb")
+            lins = [m.emb_layers[1] for m in res]
+            if any(l.weight.requires_grad for l in lins):
+                dwall = torch.zeros(ET, te, dtype=f32, device=dev)
+                ops.gemm_tn(demb, s2, dwall, N=ET, K=te, R=B)
+            if any(l.bias.requires_grad for l in lins):
+                dball = torch.zeros(ET, dtype=f32, device=dev)
+                ops.vit_colsum(demb, dball, self._colsum_ws(ET), R=B)
+            for m, l, o in zip(res, lins, self._emb_off):
+                if l.weight.requires_grad:
+                    self._acc(l.weight, dwall[o:o + m.cout])
+                if l.bias.requires_grad:
+                    self._acc(l.bias, dball[o:o + m.cout])
+            if any(p.requires_grad for p in net.time_embed.parameters()):
+                de2 = self.silu_bwd(self._dx(demb, wall, self.new(B, te), B, ET, te), e2)
+                self._wgrad(de2, lambda: s1, l2.weight, l2.bias, B, te, te)
+                if any(p.requires_grad for p in l0.parameters()):
+                    de1 = self.silu_bwd(self._dx(de2, w2, self.new(B, te), B, te, te), e1)
+                    self._wgrad(de1, lambda: temb, l0.weight, l0.bias, B, te, mc)
+        return img, backward
+
+
+class _UNetTrainStep(torch.autograd.Function):
+    """Bridges the hand-written backward of _UNetTrainF32 into autograd: the image is a leaf of the caller's loss graph, hung on one trainable
+    parameter (the anchor); the backward deposits every parameter gradient itself and hands autograd nothing."""
+
+    @staticmethod
+    def forward(ctx, anchor, engine, sample, timestep, cond, cond_mask):
+        img, ctx.bwd = engine.forward_train(sample, timestep, cond, cond_mask)
+        return img
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.bwd is None:
+            raise RuntimeError("PatchedUNetCondCat: this evaluation's backward has run already (its saved tensors are freed)")
+        ctx.bwd(g)
+        ctx.bwd = None
+        return None, None, None, None, None, None

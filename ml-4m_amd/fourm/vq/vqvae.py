@@ -12,7 +12,8 @@ autocast there, vit_models.py:494-496, quantize_lucid.py:388-390).  Code assignm
 (tests); end-to-end token agreement against the all-fp32 upstream run is measured and asserted by the tests.
 ``model.compute_precision = "fp32"`` (``VQ`` and ``DiVAE``; assigned after construction) runs the ViT encoder, the projection, the code search,
 the conditional UNet and the sampling pipeline entirely in fp32 - upstream's run without autocast - on the trunk's fp32 kernels,
-csrc/unet_f32.hip and fm_gemm_f32; ``VQVAE``, the MLP / Memcodes tokenizers and training mode refuse it (NotImplementedError)."""
+csrc/unet_f32.hip and fm_gemm_f32; ``VQVAE``, the MLP / Memcodes tokenizers and a training-mode encoder refuse it (NotImplementedError).  In that mode
+``DiVAE.forward`` with ``freeze_enc=True`` trains the diffusion decoder on the frozen encoder (csrc/unet_f32_bwd.hip); there is no bf16 backward."""
 import copy
 from typing import Any, Dict, List, Optional, Tuple, Union
 
@@ -277,7 +278,9 @@ class DiVAE(VQ):
     """Encoder + discrete bottleneck + diffusion decoder (upstream ``DiVAE``, vqvae.py:498-764): same constructor, state_dict keys
     (``decoder.*`` = the conditional UNet) and methods.  Inference runs on the HIP kernels: ``decode_quant`` / ``decode_tokens`` /
     ``autoencode`` sample with the pipeline of fourm.vq.scheduling, ``forward(input_clean, input_noised, timesteps)`` evaluates the decoder
-    once (no gradient path: the detokenizers are trained upstream).  ``uvit_*`` decoders are not built."""
+    once; with ``compute_precision = "fp32"`` and ``freeze_enc=True`` in training mode that evaluation is differentiable with respect to the
+    decoder's parameters (the decoder trained on a frozen encoder; every other combination has no gradient path).  ``uvit_*`` decoders are
+    not built."""
 
     def __init__(self, dec_type: str = "unet_patched", num_train_timesteps: int = 1000, cls_free_guidance_dropout: float = 0.0, masked_cfg: bool = False,
                  masked_cfg_low: int = 0, masked_cfg_high: Optional[int] = None, scheduler: str = "ddpm", beta_schedule: str = "squaredcos_cap_v2",
@@ -339,18 +342,35 @@ class DiVAE(VQ):
         return self._get_pipeline(scheduler)(quant, timesteps=timesteps, generator=generator, image_size=input_clean.shape[-1], verbose=verbose,
                                              scheduler_timesteps_mode=scheduler_timesteps_mode, orig_res=orig_res)
 
+    def _cfg_mask(self, quant, cond_mask):
+        """The classifier-free-guidance mask of a training step (vqvae.py:753-760): drawn when none is given."""
+        if cond_mask is None and self.cfg_dist is not None and self.training:
+            B, _, hq, wq = quant.shape
+            cond_mask = self.cfg_dist.sample((B,)).to(quant.device, dtype=torch.bool)[:, None, None].expand(B, hq, wq)
+            if self.masked_cfg:
+                cond_mask = self.sample_mask(quant, low=self.masked_cfg_low, high=self.masked_cfg_high) * cond_mask
+        return cond_mask
+
     def forward(self, input_clean: torch.Tensor, input_noised: torch.Tensor, timesteps, cond_mask: Optional[torch.Tensor] = None, orig_res=None):
-        """(dec, code_loss): encode the clean input, evaluate the diffusion decoder on the noised one (vqvae.py:716-764).  No gradient path."""
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.decoder.parameters()) and self.training:
-            raise NotImplementedError("DiVAE.forward has no backward here (the diffusion decoder is inference-only): call under torch.no_grad() / .eval()")
+        """(dec, code_loss): encode the clean input, evaluate the diffusion decoder on the noised one (vqvae.py:716-764).
+
+        Training the decoder on a frozen encoder (upstream's recommended workflow): with ``compute_precision = "fp32"``, ``freeze_enc=True``, in
+        training mode, with gradients enabled and a trainable decoder parameter, ``dec`` is differentiable with respect to the decoder's
+        parameters (PatchedUNetCondCat's verification-mode backward).  The clean input is encoded without gradients and with the frozen
+        quantizer left alone (no EMA codebook update: upstream's ``train()`` keeps the frozen modules in eval mode); ``code_loss`` is zero.
+        Not built: a bf16 backward, a gradient to the conditioning or the encoder (end-to-end training), non-square inputs, graph capture."""
+        from .engine import vq_encode
+        frozen = self.freeze_enc and self.compute_precision == "fp32"
+        needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.decoder.parameters()) and self.training
+        if needs_grad and not frozen:
+            raise NotImplementedError("DiVAE.forward has a backward only with compute_precision = \"fp32\" and freeze_enc=True (the diffusion decoder "
+                                      "trained on a frozen encoder); this combination is inference-only: call under torch.no_grad() / .eval()")
         with torch.no_grad():
-            quant, code_loss, _ = self._encode(input_clean)
-            if cond_mask is None and self.cfg_dist is not None and self.training:
-                B, _, hq, wq = quant.shape
-                cond_mask = self.cfg_dist.sample((B,)).to(quant.device, dtype=torch.bool)[:, None, None].expand(B, hq, wq)
-                if self.masked_cfg:
-                    cond_mask = self.sample_mask(quant, low=self.masked_cfg_low, high=self.masked_cfg_high) * cond_mask
-            dec = self.decoder(input_noised, timesteps, quant, cond_mask=cond_mask, orig_res=orig_res)
+            # frozen: the inference encoder in training mode too - the quantizer is only read (self._encode would move the codebook)
+            quant, code_loss, _ = vq_encode(self, self.prepare_input(input_clean)) if frozen else self._encode(input_clean)
+            cond_mask = self._cfg_mask(quant, cond_mask)
+        with torch.enable_grad() if needs_grad else torch.no_grad():
+            dec = self.decoder(input_noised.detach(), timesteps, quant, cond_mask=cond_mask, orig_res=orig_res)
         return dec, code_loss
 
 
