@@ -285,6 +285,9 @@ typedef struct fm_select_desc {
     int32_t rows_f32;   /* 1: patch_rows / seqemb_rows are f32 (fp32 verification path)                     */
     int32_t pad2_;
 } fm_select_desc;
+/* Limits (refused with -1 otherwise): 1 <= n_mods <= FM_MAX_MODS; dim % 4 == 0; total_len = sum of the L, at most 8192 concatenated
+ * positions per sample; n_keep <= total_len and at most 1024 kept slots (8192 in the raw views, which need n_keep == total_len and
+ * n_reg == 0); patch_ld % 4 == seqemb_ld % 4 == 0.  Register rows carry zero patch_rows / seqemb_rows like every other non-dense slot. */
 int fm_select_embed(const fm_select_desc* desc, void* stream);
 
 typedef struct fm_embed_bwd_mod {
@@ -302,6 +305,9 @@ typedef struct fm_embed_bwd_desc {
     void* d_reg_tokens;      /* encoder, (n_reg, D) */
     int32_t n_mods, batch, dim, Nt, lddx, is_decoder;
 } fm_embed_bwd_desc;
+/* Accumulates (fp32 atomics) into every non-NULL gradient buffer; NULL ones are skipped.  Limits (refused with -1 otherwise):
+ * 1 <= n_mods <= FM_MAX_MODS; dim % 4 == 0 and dim <= 2048; lddx % 4 == 0; the per-modality column sums live in LDS, so
+ * (n_mods + 1) * dim * 4 bytes must not exceed 150 KB (24 modalities at dim 2048 do). */
 int fm_embed_bwd(const fm_embed_bwd_desc* desc, void* stream);
 
 /* dense (B, M, M) uint8 mask from the compressed form (FourM.adapt_decoder_attention_mask, fm.py:440-475) */

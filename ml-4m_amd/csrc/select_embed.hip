@@ -151,6 +151,16 @@ __global__ __launch_bounds__(256) void select_embed_kernel(SelArgs A) {
                 ((int32_t*)d.slot_src)[orow] = s;
                 ((int32_t*)d.slot_pos)[orow] = 0;
             }
+            // no dense side input: the projection GEMMs run over every row, registers included ("zero elsewhere" in the header)
+            const int esz = d.rows_f32 ? 2 : 1;                  // uint2 stores per 4 elements
+            if (d.patch_rows) {
+                uint2* pr = (uint2*)((char*)d.patch_rows + orow * d.patch_ld * (size_t)(2 * esz));
+                for (int f = lane; f < d.patch_ld / 4 * esz; f += 64) pr[f] = make_uint2(0u, 0u);
+            }
+            if (d.seqemb_rows) {
+                uint2* sr = (uint2*)((char*)d.seqemb_rows + orow * d.seqemb_ld * (size_t)(2 * esz));
+                for (int f = lane; f < d.seqemb_ld / 4 * esz; f += 64) sr[f] = make_uint2(0u, 0u);
+            }
             continue;
         }
         const int sk = s - d.n_reg;
