@@ -37,7 +37,10 @@ enum fm_epilogue {
     FM_EPI_TANH = 5,     /* out(bf16)  = tanh(bf16(acc + bias))                                       */
     FM_EPI_SWIGLU_BWD = 6, /* acc = d(silu(g)*u); res(bf16,(M,2*Hp)) = g|u saved by FM_EPI_SWIGLU;
                               out(bf16,(M,2*Hp)) = dg | du.  Columns [roundup4(N), Hp) of each half are not written */
-    FM_EPI_GELU_BWD = 7  /* acc = d(gelu(pre)); res(bf16) = pre saved by FM_EPI_GELU; out(bf16) = d(pre) */
+    FM_EPI_GELU_BWD = 7, /* acc = d(gelu(pre)); res(bf16) = pre saved by FM_EPI_GELU; out(bf16) = d(pre) */
+    FM_EPI_QUICK_GELU = 8 /* CLIP's QuickGELU: pre = bf16(acc + bias); out(bf16) = pre / (1 + exp(-1.702 pre)); out2(bf16, optional) = pre.
+                             Accepted wherever FM_EPI_GELU is (same kernels, same dispatch) and by the few-row kernel; large |pre| gives
+                             +-0 or pre, never NaN */
 };
 
 typedef struct fm_gemm_group {  /* one entry per row segment (modality) in grouped mode */
@@ -400,6 +403,18 @@ int fm_scale_rows_bf16(void* x, int ld, const void* scale, int rows_per_sample, 
 int fm_vit_patch_rows(const void* pixels, void* rows, int ld, int B, int C, int H, int W, int P, int rows_f32, void* stream);
 int fm_vit_emb_rows(const void* pos, const void* mod_emb, void* x, int ldx, int B, int Np, int D, void* stream);
 int fm_vit_colsum(const void* dy, int ldy, void* db, int R, int N, void* ws, int64_t ws_bytes, void* stream);
+
+/* Front end of CLIP's VisionTransformer (fourm/utils/clip/model.py:229-237: cat(class_embedding, conv1 patches) + positional_embedding,
+ * then ln_pre), csrc/clip.hip.  patches: the (B * G, D) output rows of the bias-free conv1-as-GEMM, row stride ldp, bf16 or (patches_f32)
+ * f32; cls (D), pos ((G + 1, D), contiguous), w / b (ln_pre, D): f32.  out: the f32 residual stream (B * (G + 1), D), row stride ldo:
+ *   out[b (G + 1)]         = LN(cls + pos[0])
+ *   out[b (G + 1) + 1 + g] = LN(patches[b G + g] + pos[1 + g])
+ * One pass, one wavefront per row, the row in registers, fp32 statistics (eps inside the sqrt), 16-byte accesses (8 bytes for bf16 rows).
+ * Rows of patches past B * G are not read, rows of out past B * (G + 1) and columns past D are not written.
+ * Refused (-1): null pointers (b may be NULL: no bias), B, G or D not positive, D not a multiple of 4 or > 2048, ldp / ldo smaller than D
+ * or not multiples of 4, pointers not 16-byte aligned, more than 2^31 - 1 output rows. */
+int fm_clip_embed_ln(const void* patches, int ldp, int patches_f32, const void* cls, const void* pos, const void* w, const void* b,
+                     void* out, int ldo, int B, int G, int D, float eps, void* stream);
 
 /* Low-rank adapters (LoRAWrapper, fourm/models/lora_utils.py:44-81: y = linear(x) + scale * lora_up(lora_down(x))), csrc/lora.hip.
  * P = x down^T (fp32 accumulation over K), y += scale * P up^T in place (fp32 sum, rounded once to y's type), P written to p_out.

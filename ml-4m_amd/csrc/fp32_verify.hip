@@ -15,6 +15,7 @@ namespace {
 constexpr float NEG_FILL32 = -3.4028234663852886e38f;     // -finfo(float32).max
 
 __device__ __forceinline__ float gelu32(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
+__device__ __forceinline__ float qgelu32(float x) { return x / (1.0f + expf(-1.702f * x)); }       // CLIP's QuickGELU (x / inf = +-0 for large -x)
 __device__ __forceinline__ float sigm32(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -86,6 +87,10 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(fm_gemm_f32_args a) {
                 case FM_EPI_GELU:
                     if (out2) out2[(size_t)m * a.ldo2 + n] = v;
                     *o = gelu32(v);
+                    break;
+                case FM_EPI_QUICK_GELU:
+                    if (out2) out2[(size_t)m * a.ldo2 + n] = v;
+                    *o = qgelu32(v);
                     break;
                 case FM_EPI_TANH: *o = tanhf(v); break;
                 case FM_EPI_RESIDUAL: *o = res[(size_t)m * a.ldr + n] + v; break;
@@ -191,6 +196,7 @@ __global__ __launch_bounds__(256) void gemm_f32_mfma_kernel(fm_gemm_f32_args a) 
                     float* o = out + (size_t)m * a.ldo + n + e;
                     if (a.epilogue == FM_EPI_TANH) v = tanhf(v);
                     else if (a.epilogue == FM_EPI_GELU) { if (a.out2) ((float*)a.out2)[(size_t)m * a.ldo2 + n + e] = v; v = gelu32(v); }
+                    else if (a.epilogue == FM_EPI_QUICK_GELU) { if (a.out2) ((float*)a.out2)[(size_t)m * a.ldo2 + n + e] = v; v = qgelu32(v); }
                     else if (a.epilogue == FM_EPI_RESIDUAL || (a.epilogue == FM_EPI_F32 && res)) v += res[(size_t)m * a.ldr + n + e];
                     *o = a.accumulate ? *o + v : v;
                 }

@@ -430,9 +430,9 @@ __global__ __launch_bounds__(WW * WX * 64) void gemm_nt_kernel(NTArgs a) {
                     }
                 }
             }
-        } else if constexpr (EPI == EPI_BF16 || EPI == EPI_GELU || EPI == EPI_TANH) {
+        } else if constexpr (EPI == EPI_BF16 || is_gelu_like<EPI> || EPI == EPI_TANH) {
             bf16_t* orow = (bf16_t*)a.out + (size_t)m * a.ldo;
-            bf16_t* prow = (EPI == EPI_GELU && a.out2) ? (bf16_t*)a.out2 + (size_t)m * a.ldo2 : nullptr;
+            bf16_t* prow = (is_gelu_like<EPI> && a.out2) ? (bf16_t*)a.out2 + (size_t)m * a.ldo2 : nullptr;
             const bool wide = ((N | a.ldo | (prow ? a.ldo2 : 0)) & 7) == 0 && (((uintptr_t)a.out | (uintptr_t)(prow ? a.out2 : nullptr)) & 15) == 0;
 #pragma unroll
             for (int i = 0; i < FW; ++i) {
@@ -448,10 +448,10 @@ __global__ __launch_bounds__(WW * WX * 64) void gemm_nt_kernel(NTArgs a) {
                     }
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * g + e] + bfround(b[e]);
-                    if constexpr (EPI == EPI_GELU) {
+                    if constexpr (is_gelu_like<EPI>) {
                         pp[g] = make_uint2(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]));
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = gelu_f(bfround(v[e]));
+                        for (int e = 0; e < 4; ++e) v[e] = gelu_like_f<EPI>(bfround(v[e]));
                     } else if constexpr (EPI == EPI_TANH) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) v[e] = tanhf(bfround(v[e]));
@@ -461,7 +461,7 @@ __global__ __launch_bounds__(WW * WX * 64) void gemm_nt_kernel(NTArgs a) {
                 // one output after the other (the pieces of a 128-byte line leave back to back; see the SwiGLU epilogue)
 #pragma unroll
                 for (int g = 0; g < 4; g += 2) store_bf16_groups(orow, nb + 8 * g, po[g], po[g + 1], fhi, N, wide);
-                if constexpr (EPI == EPI_GELU) {
+                if constexpr (is_gelu_like<EPI>) {
                     if (prow) {
 #pragma unroll
                         for (int g = 0; g < 4; g += 2) store_bf16_groups(prow, nb + 8 * g, pp[g], pp[g + 1], fhi, N, wide);
@@ -1391,6 +1391,7 @@ extern "C" int fm_gemm_nt(const fm_gemm_nt_args* p, void* stream) {
     switch (p->epilogue) {
         case FM_EPI_BF16: return launch_nt<EPI_BF16, false>(a, max_n, s);
         case FM_EPI_GELU: return launch_nt<EPI_GELU, false>(a, max_n, s);
+        case FM_EPI_QUICK_GELU: return launch_nt<EPI_QGELU, false>(a, max_n, s);
         case FM_EPI_RESIDUAL:
             FM_CHECK_ARG(p->res && p->ldr % 4 == 0, "fm_gemm_nt: residual epilogue needs res / ldr%%4==0");
             return launch_nt<EPI_RES, false>(a, max_n, s);

@@ -6,7 +6,7 @@
 namespace fmk {
 
 enum { EPI_BF16 = FM_EPI_BF16, EPI_GELU = FM_EPI_GELU, EPI_RES = FM_EPI_RESIDUAL, EPI_SWIGLU = FM_EPI_SWIGLU,
-       EPI_F32 = FM_EPI_F32, EPI_TANH = FM_EPI_TANH, EPI_SWIGLU_BWD = FM_EPI_SWIGLU_BWD, EPI_GELU_BWD = FM_EPI_GELU_BWD };
+       EPI_F32 = FM_EPI_F32, EPI_TANH = FM_EPI_TANH, EPI_SWIGLU_BWD = FM_EPI_SWIGLU_BWD, EPI_GELU_BWD = FM_EPI_GELU_BWD, EPI_QGELU = FM_EPI_QUICK_GELU };
 
 struct NTArgs {
     const bf16_t* W; const bf16_t* W2; const bf16_t* X;
@@ -29,6 +29,11 @@ struct NTArgs {
 };
 
 __device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.0f + erf_fast(x * 0.70710678118654752f)); }
+// CLIP's QuickGELU x * sigmoid(1.702 x).  Large |x|: exp -> inf gives x * rcp(inf) = x * 0 = +-0, exp -> 0 gives x * 1 = x (no inf * 0)
+__device__ __forceinline__ float quick_gelu_f(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-1.702f * x)); }
+// the two activations that share every GELU code path (out = act(bf16(pre)), out2 = pre)
+template <int EPI> constexpr bool is_gelu_like = EPI == EPI_GELU || EPI == EPI_QGELU;
+template <int EPI> __device__ __forceinline__ float gelu_like_f(float x) { if constexpr (EPI == EPI_QGELU) return quick_gelu_f(x); else return gelu_f(x); }
 __device__ __forceinline__ float silu_f(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 
 

@@ -65,7 +65,7 @@ __global__ __launch_bounds__(512) void gemm_nt3_kernel(NTArgs a) {
     constexpr int NPT = (EPI == EPI_SWIGLU) ? TW / 2 : TW;
     constexpr int NMF = FW * FX;                                    // MFMAs per k-step
     // stores per wave and tile (16 bytes per lane each)
-    constexpr int NST = (EPI == EPI_BF16 || EPI == EPI_GELU) ? FW * FX * 2 : EPI == EPI_SWIGLU ? FX * (FW / 2) * 2 * 3 : EPI == EPI_SWIGLU_BWD ? 60 : FW * FX * 4;
+    constexpr int NST = (EPI == EPI_BF16 || is_gelu_like<EPI>) ? FW * FX * 2 : EPI == EPI_SWIGLU ? FX * (FW / 2) * 2 * 3 : EPI == EPI_SWIGLU_BWD ? 60 : FW * FX * 4;
     static_assert(TW % (RPP * NWAVES) == 0, "tile rows must split evenly over the DMA pieces");
     static_assert(EPI != EPI_SWIGLU || FW % 2 == 0, "SwiGLU needs (g,u) fragment pairs per wave");
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -164,21 +164,21 @@ __global__ __launch_bounds__(512) void gemm_nt3_kernel(NTArgs a) {
     auto finish_tile = [&](int j_done) __attribute__((always_inline)) {
         int n0, m0;
         tile_origin(j_done, n0, m0);
-        if constexpr ((EPI == EPI_BF16 || EPI == EPI_GELU) && STG) {
+        if constexpr ((EPI == EPI_BF16 || is_gelu_like<EPI>) && STG) {
             const __amdgpu_buffer_rsrc_t rs_out = rsrc_of((const char*)a.out + (size_t)m0 * a.ldo * 2);
             const __amdgpu_buffer_rsrc_t rs_pre = rsrc_of((const char*)(a.out2 ? a.out2 : a.out) + (size_t)m0 * (a.out2 ? a.ldo2 : a.ldo) * 2);
             (void)rs_pre;
             constexpr int CW = (TW / WW) / 8;                                   // 16-byte chunks per staged row: 16 (two rounds of 8) or 12
             constexpr int RCH = CW == 16 ? 8 : 12, ROWB = RCH * 16, NRND = CW / RCH, SPR = 32 * RCH / 64;     // stores per round
             char* sc = smem + 2 * STAGE + wave * (32 * ROWB);
-            constexpr int NWHICH = EPI == EPI_GELU ? 2 : 1;                     // GELU: the pre-activation (when asked for), then the activation
+            constexpr int NWHICH = is_gelu_like<EPI> ? 2 : 1;                     // GELU: the pre-activation (when asked for), then the activation
 #pragma unroll
             for (int j = 0; j < FX; ++j)
 #pragma unroll
                 for (int rnd = 0; rnd < NRND; ++rnd)
 #pragma unroll
                 for (int which = 0; which < NWHICH; ++which) {
-                    if (EPI == EPI_GELU && which == 0 && !a.out2) continue;
+                    if (is_gelu_like<EPI> && which == 0 && !a.out2) continue;
 #pragma unroll
                     for (int ii = 0; ii < RCH / 4; ++ii)
 #pragma unroll
@@ -192,9 +192,9 @@ __global__ __launch_bounds__(512) void gemm_nt3_kernel(NTArgs a) {
                                     v[0] += bfround(t.x); v[1] += bfround(t.y); v[2] += bfround(t.z); v[3] += bfround(t.w);
                                 }
                             }
-                            if (EPI == EPI_GELU && which == 1) {
+                            if (is_gelu_like<EPI> && which == 1) {
 #pragma unroll
-                                for (int e = 0; e < 4; ++e) v[e] = gelu_f(bfround(v[e]));
+                                for (int e = 0; e < 4; ++e) v[e] = gelu_like_f<EPI>(bfround(v[e]));
                             }
                             const uint2 pv = make_uint2(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]));
                             int pos;
@@ -221,7 +221,7 @@ __global__ __launch_bounds__(512) void gemm_nt3_kernel(NTArgs a) {
                     for (int q = 0; q < SPR; ++q) {
                         const int rl = wx * (TX / WX) + j * 32 + rr[q];
                         const int c = n0 + ww * (TW / WW) + rnd * (RCH * 8) + cc[q] * 8;
-                        if (EPI == EPI_GELU && which == 0) {
+                        if (is_gelu_like<EPI> && which == 0) {
                             const uint32_t so = ((m0 + rl < a.M && c < N) ? 0u : OOB) | ((uint32_t)(rl * a.ldo2) * 2u + (uint32_t)c * 2u);
                             __builtin_amdgcn_raw_buffer_store_b128(rv[q], rs_pre, so, 0, 0);
                         } else {
@@ -621,7 +621,7 @@ int fm_launch_nt3(const fmk::NTArgs& a, int epilogue, int mode, hipStream_t s) {
         if ((size_t)256 * (size_t)a.ldo * 4 >= 0x7fffffffull || (size_t)256 * (size_t)a.ldx * 2 >= 0x7fffffffull || (size_t)256 * (size_t)a.ldw * 2 >= 0x7fffffffull) return 0;
         return (a.N % 192 == 0 && a.N % 256 != 0) ? launch_nt3<192, EPI_BF16, true, true, false, true>(a, s) : launch_nt3<256, EPI_BF16, true, true, false, true>(a, s);
     }
-    if (a.bias && !(epilogue == FM_EPI_BF16 || epilogue == FM_EPI_GELU)) return 0;
+    if (a.bias && !(epilogue == FM_EPI_BF16 || epilogue == FM_EPI_GELU || epilogue == FM_EPI_QUICK_GELU)) return 0;
     if (a.bias && ((((uintptr_t)a.bias) & 15) != 0 || (a.lab & (16 | 1024)))) return 0;       // (biased launches exist in the staged form only)
     if (a.M < 2048 || a.K % 64 != 0 || a.K < 128 || a.N % 8 != 0) return 0;
     if ((size_t)256 * (size_t)a.ldo * 4 >= 0x7fffffffull || (size_t)256 * (size_t)a.ldx * 2 >= 0x7fffffffull || (size_t)256 * (size_t)a.ldw * 2 >= 0x7fffffffull) return 0;
@@ -644,6 +644,12 @@ int fm_launch_nt3(const fmk::NTArgs& a, int epilogue, int mode, hipStream_t s) {
         if (a.ldo % 64 != 0 || (((uintptr_t)a.out) & 127) != 0 || (a.out2 && (a.ldo2 % 64 != 0 || (((uintptr_t)a.out2) & 127) != 0)) || (a.lab & (16 | 1024))) return 0;
         if (a.bias) return use192 ? launch_nt3<192, EPI_GELU, true, true, true>(a, s) : launch_nt3<256, EPI_GELU, true, true, true>(a, s);
         return use192 ? launch_nt3<192, EPI_GELU, true, true, false>(a, s) : launch_nt3<256, EPI_GELU, true, true, false>(a, s);
+    }
+    if (epilogue == FM_EPI_QUICK_GELU) {      // CLIP's c_fc: FM_EPI_GELU's conditions and gate, so that the launch takes the route the tokenizer's fc1 takes
+        if (!(a.lab & 131072)) return 0;
+        if (a.ldo % 64 != 0 || (((uintptr_t)a.out) & 127) != 0 || (a.out2 && (a.ldo2 % 64 != 0 || (((uintptr_t)a.out2) & 127) != 0)) || (a.lab & (16 | 1024))) return 0;
+        if (a.bias) return use192 ? launch_nt3<192, EPI_QGELU, true, true, true>(a, s) : launch_nt3<256, EPI_QGELU, true, true, true>(a, s);
+        return use192 ? launch_nt3<192, EPI_QGELU, true, true, false>(a, s) : launch_nt3<256, EPI_QGELU, true, true, false>(a, s);
     }
     if (epilogue == FM_EPI_BF16) {
         if (a.ldo % 8 != 0) return 0;

@@ -7,7 +7,8 @@
 // K / 64 MFMAs (v_mfma_f32_32x32x16_bf16, W rows on the MFMA row side, the <= 32 token rows on the column side), the partial sums meet in
 // LDS and every wave finishes a quarter of the features.  N / 32 workgroups: 72 for qkv, 24 for a 768-wide projection, 938 for a 30 000-word
 // head - the weights stream from HBM at the rate the whole chip pulls, and the launch is a few microseconds of latency.
-// Epilogues as in gemm.hip, bit for bit: bf16 (+ bias), fp32 residual (+ bias), SwiGLU (two weights; act and optionally g | u).
+// Epilogues as in gemm.hip, bit for bit: bf16 (+ bias), fp32 residual (+ bias), SwiGLU (two weights; act and optionally g | u), QuickGELU
+// (act and optionally the pre-activation; the class-token rows of CLIP's tower).
 #include "common.h"
 #include "fourm_hip.h"
 #include "gemm_args.h"
@@ -84,6 +85,16 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(NTArgs a) {
         bf16_t* o = (bf16_t*)a.out + (size_t)fr * a.ldo + nb;
 #pragma unroll
         for (int e = 0; e < 4; ++e) if (nb + e < N) o[e] = f2bf(v[e] + b[e]);
+    } else if constexpr (EPI == EPI_QGELU) {
+        bf16_t* o = (bf16_t*)a.out + (size_t)fr * a.ldo + nb;
+        bf16_t* pre = a.out2 ? (bf16_t*)a.out2 + (size_t)fr * a.ldo2 + nb : nullptr;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (nb + e >= N) continue;
+            const float p = bfround(v[e] + b[e]);
+            o[e] = f2bf(quick_gelu_f(p));
+            if (pre) pre[e] = f2bf(p);
+        }
     } else if constexpr (EPI == EPI_RES) {
         float* o = (float*)a.out + (size_t)fr * a.ldo + nb;
         const float* rr = a.res + (size_t)fr * a.ldr + nb;
@@ -114,6 +125,7 @@ int fm_launch_nt_skinny(const fmk::NTArgs& a, int epilogue, hipStream_t s) {
     if (epilogue == FM_EPI_BF16) hipLaunchKernelGGL(gemm_skinny_kernel<EPI_BF16>, grid, dim3(256), 0, s, a);
     else if (epilogue == FM_EPI_RESIDUAL && a.res) hipLaunchKernelGGL(gemm_skinny_kernel<EPI_RES>, grid, dim3(256), 0, s, a);
     else if (epilogue == FM_EPI_SWIGLU && a.W2) hipLaunchKernelGGL(gemm_skinny_kernel<EPI_SWIGLU>, grid, dim3(256), 0, s, a);
+    else if (epilogue == FM_EPI_QUICK_GELU) hipLaunchKernelGGL(gemm_skinny_kernel<EPI_QGELU>, grid, dim3(256), 0, s, a);
     else return 0;
     if (hipGetLastError() != hipSuccess) return -2;
     return 1;

@@ -675,7 +675,9 @@ class FourMEngine:
         else:
             pre = self._buf(sv, tag, "pre", (Rp, self.Hp), bf) if sv is not None else None     # inference: nothing to save
             act = self._buf(sv, tag, "act", (Rp, self.Hp), bf)
-            ops.gemm_nt(h, self.w(mlp.fc1.weight), act, epilogue=L.EPI_GELU, out2=pre, bias=mlp.fc1.bias, M=R, N=self.Hd, K=self.D)
+            # ("quick_gelu": CLIP's tower, fourm/utils/clip/model.py - inference only, so pre is never asked for there)
+            ops.gemm_nt(h, self.w(mlp.fc1.weight), act, epilogue=L.EPI_QUICK_GELU if self.act == "quick_gelu" else L.EPI_GELU, out2=pre, bias=mlp.fc1.bias,
+                        M=R, N=self.Hd, K=self.D)
         self._residual(act, mlp.fc2, x_res, x_out, R, self.D, self.Hp, defer)
 
     def _qk_norm_fwd(self, attn, q, k, Rq, Rk, Rqp, Rkp, sv, tag, key):
