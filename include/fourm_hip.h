@@ -416,6 +416,38 @@ int fm_vit_colsum(const void* dy, int ldy, void* db, int R, int N, void* ws, int
 int fm_clip_embed_ln(const void* patches, int ldp, int patches_f32, const void* cls, const void* pos, const void* w, const void* b,
                      void* out, int ldo, int B, int G, int D, float eps, void* stream);
 
+/* Backward of a FROZEN CLIP tower, for the perceptual loss of tokenizer training (upstream fourm/vq/percept_losses/timm_perceptual_loss.py:89-109:
+ * features of the reconstruction and of the image after some blocks, compared token by token).  csrc/clip.hip, csrc/elementwise.hip.
+ *
+ * fm_feat_distance: pred / tgt f32 (B * T, ld) feature rows of one tap.  Per sample b the value of this tap,
+ *       FM_FEAT_COSINE: (1 - mean_t cos(p_t, t_t)) / B,  cos = <p, t> / (max(|p|, 1e-8) max(|t|, 1e-8))      (F.cosine_similarity)
+ *       FM_FEAT_L1:     (mean_t sum_d |p^_d - t^_d|) / B,  x^ = x / max(|x|, 1e-12)                          (F.normalize + l1_loss)
+ *   is ADDED to loss[b] (f32 (B,); the 1 / B is upstream's own division of the per-sample vector by the batch size), and its gradient
+ *   with respect to pred is written to dpred f32 (B * T, lddp) (sign(0) = 0; below the clamp the norm is a constant, as in torch).
+ *   One workgroup per sample: a wavefront reduces a token over D, keeps its tokens' sum in token order, the 16 partial sums are added
+ *   in wave order - no atomics, the same bits on every run.  tgt receives no gradient.
+ *   Refused (-1): null pointers, B, T or D not positive, D not a multiple of 4 or > 2048, a leading dimension below D or not a multiple
+ *   of 4, pointers not 16-byte aligned, a mode other than the two.
+ * fm_quick_gelu_bwd / fm_quick_gelu_bwd_f32: a = u sigmoid(1.702 u) -> dpre = da s (1 + 1.702 u (1 - s)), s = sigmoid(1.702 u), u the saved
+ *   pre-activation.  Signatures and layout rules of fm_gelu_bwd (bf16: Hp and the leading dims multiples of 4, columns [H, Hp) written
+ *   as zero) and fm_gelu_bwd_f32 (columns past H untouched).
+ * fm_clip_embed_ln_bwd: the adjoint of fm_clip_embed_ln with respect to the patch rows.  dy f32 (B * (G + 1), lddy): gradient of the
+ *   normalised stream rows.  Each pre-norm patch row is rebuilt from patches + pos, its statistics recomputed, and
+ *   d_patches[b * G + g] = rstd (dy w - mean(dy w) - x_hat mean(dy w x_hat)) written as bf16 or f32 rows (as patches_f32 says, row
+ *   stride lddp); the class rows are skipped.  Refusals as fm_clip_embed_ln.
+ * fm_tap_add: g[r] += row_scale[r / rows_per_sample] * dtap[r] on f32 (R, D) tiles (row_scale f32 per sample, or NULL: 1; product and sum
+ *   rounded separately), then g_bf[r] = bf16(g[r]) unless g_bf is NULL: a tap's gradient enters the stream gradient in front of the block
+ *   below it.  D, ldg, ldt, ldgb multiples of 4, g / dtap 16-byte and g_bf 8-byte aligned. */
+enum { FM_FEAT_COSINE = 0, FM_FEAT_L1 = 1 };
+int fm_feat_distance(const void* pred, int ldp, const void* tgt, int ldt, int B, int T, int D, int mode, void* loss, void* dpred, int lddp,
+                     void* stream);
+int fm_quick_gelu_bwd(const void* da, int ldda, const void* pre, int ldp, void* dpre, int lddp, int R, int H, int Hp, void* stream);
+int fm_quick_gelu_bwd_f32(const void* da, int ldda, const void* pre, int ldp, void* dpre, int lddp, int R, int H, void* stream);
+int fm_clip_embed_ln_bwd(const void* dy, int lddy, const void* patches, int ldp, int patches_f32, const void* pos, const void* w,
+                         void* d_patches, int lddp, int B, int G, int D, float eps, void* stream);
+int fm_tap_add(void* g, int ldg, void* g_bf, int ldgb, const void* dtap, int ldt, const void* row_scale, int rows_per_sample, int R, int D,
+               void* stream);
+
 /* Low-rank adapters (LoRAWrapper, fourm/models/lora_utils.py:44-81: y = linear(x) + scale * lora_up(lora_down(x))), csrc/lora.hip.
  * P = x down^T (fp32 accumulation over K), y += scale * P up^T in place (fp32 sum, rounded once to y's type), P written to p_out.
  * x: (R, K) row stride ldx; y: (R, N) row stride ldy; x_f32 / y_f32 select fp32 instead of bf16 elements (bf16 x with fp32 y is
@@ -500,9 +532,14 @@ typedef struct fm_gemm_f32_args {
 } fm_gemm_f32_args;
 int fm_gemm_f32(const fm_gemm_f32_args* args, void* stream);
 /* fm_attn_args with f32 Q / K / V / O (/ dO, dQ, dK, dV); blocked scores are replaced by -finfo(float32).max; stat_m / stat_l
- * unused.  The backward ACCUMULATES into dK and dV (the caller zeroes them). */
+ * unused by the forward.  The backward ACCUMULATES into dK and dV (the caller zeroes them).  Backward without stat_m / stat_l: every query's
+ * contribution to dK / dV arrives by an fp32 atomic (the sum's order, and with it the last bits, vary from run to run).  With both given
+ * ((B, H, Nq) f32 each, used as SCRATCH: row max and 1 / row sum) and O holding the forward's output: dQ as before, then dK / dV by a second
+ * launch in which one wavefront per key row adds the queries in order - no atomics, the same bits on every run. */
 int fm_attn_f32_fwd(const fm_attn_args* args, void* stream);
 int fm_attn_f32_bwd(const fm_attn_args* args, void* stream);
+/* fm_layernorm_bwd_f32 (dw, db) and fm_colsum_f32 (db) ACCUMULATE column sums over the rows in a fixed order (64 columns per workgroup, 16 row
+ * groups added in group order; no atomics): two runs give the same bits. */
 int fm_layernorm_bwd_f32(const void* dy, int lddy, const int32_t* dy_row_map, const void* x, int ldx, const void* w, const void* mean,
                          const void* rstd, const void* dres, void* dx, int lddx, void* dx2, int lddx2, void* dw, void* db, int R, int D,
                          void* stream);

@@ -76,6 +76,67 @@ __global__ __launch_bounds__(256) void gelu_bwd_kernel(const bf16_t* __restrict_
     }
 }
 
+// a = u sigmoid(1.702 u)  ->  dpre = da * s (1 + 1.702 u (1 - s)),  s = sigmoid(1.702 u)        (QuickGELU of CLIP's MLP, clip/model.py)
+// F32 = false: bf16 tiles, 4 features per thread, columns [H, Hp) written as zero (gelu_bwd_kernel's layout).
+// F32 = true: f32 tiles of any stride, one feature per thread, nothing past column H is touched (gelu_bwd_f32_kernel's layout).
+template <bool F32>
+__global__ __launch_bounds__(256) void quick_gelu_bwd_kernel(const void* __restrict__ da_, int ldda, const void* __restrict__ pre_, int ldp,
+                                                             void* __restrict__ dpre_, int lddp, int R, int H, int Hp) {
+    if constexpr (F32) {
+        const float *da = (const float*)da_, *pre = (const float*)pre_;
+        float* dpre = (float*)dpre_;
+        const size_t total = (size_t)R * H;
+        for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+            const size_t r = i / H, c = i % H;
+            const float u = pre[r * ldp + c];
+            const float s = 1.0f / (1.0f + expf(-1.702f * u));
+            dpre[r * lddp + c] = da[r * ldda + c] * (s * (1.0f + 1.702f * u * (1.0f - s)));
+        }
+    } else {
+        const bf16_t *da = (const bf16_t*)da_, *pre = (const bf16_t*)pre_;
+        bf16_t* dpre = (bf16_t*)dpre_;
+        const int cpr = Hp / 4;
+        const size_t total = (size_t)R * cpr;
+        for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+            const size_t r = i / cpr;
+            const int c = (int)(i % cpr) * 4;
+            const float4 d = ld_bf4(da + r * ldda + c), x = ld_bf4(pre + r * ldp + c);
+            const float dv[4] = {d.x, d.y, d.z, d.w}, xv[4] = {x.x, x.y, x.z, x.w};
+            float o[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float s = sigmoid_f(1.702f * xv[e]);
+                o[e] = (c + e < H) ? dv[e] * (s * (1.0f + 1.702f * xv[e] * (1.0f - s))) : 0.f;
+            }
+            st_bf4(dpre + r * lddp + c, o[0], o[1], o[2], o[3]);
+        }
+    }
+}
+
+// g += row_scale[r / rows_per_sample] * dtap (product and sum rounded separately: the fp32 result of the two torch operations), then
+// g_bf = bf16(g): a tap's gradient joins the stream gradient (fourm/vq/percept_losses).  4 features per thread, 16-byte accesses.
+__global__ __launch_bounds__(256) void tap_add_kernel(float* __restrict__ g, int ldg, bf16_t* __restrict__ g_bf, int ldgb, const float* __restrict__ dtap, int ldt,
+                                                      const float* __restrict__ row_scale, int rows_per_sample, int R, int D) {
+#pragma clang fp contract(off)          // no fused multiply-add in this function: s * d is rounded before it is added
+    const int cpr = D / 4;
+    const size_t total = (size_t)R * cpr;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const size_t r = i / cpr;
+        const int c = (int)(i % cpr) * 4;
+        const float4 a = *(const float4*)(g + r * ldg + c), d = *(const float4*)(dtap + r * ldt + c);
+        float4 o;
+        if (row_scale) {
+            const float s = row_scale[r / rows_per_sample];
+            const float px = s * d.x, py = s * d.y, pz = s * d.z, pw = s * d.w;
+            o = make_float4(a.x + px, a.y + py, a.z + pz, a.w + pw);
+        } else {
+            o = make_float4(a.x + d.x, a.y + d.y, a.z + d.z, a.w + d.w);
+        }
+        *(float4*)(g + r * ldg + c) = o;
+        if (g_bf) st_bf4(g_bf + r * ldgb + c, o.x, o.y, o.z, o.w);
+    }
+}
+
 // dst (rows, ldd) bf16 <- src (rows, cols) f32, columns [cols, ldd) zero
 __global__ __launch_bounds__(256) void cast_pad_kernel(const float* __restrict__ src, int lds_, bf16_t* __restrict__ dst, int ldd, int rows, int cols) {
     const int cpr = ldd / 4;
@@ -450,6 +511,42 @@ extern "C" int fm_gelu_bwd(const void* dh, int lddh, const void* pre, int ldp, v
     hipLaunchKernelGGL(gelu_bwd_kernel, dim3(grid_for((size_t)R * Hp / 4)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dh, lddh,
                        (const bf16_t*)pre, ldp, (bf16_t*)dpre, lddp, R, H, Hp);
     FM_CHECK_LAUNCH("fm_gelu_bwd");
+    return 0;
+}
+
+extern "C" int fm_quick_gelu_bwd(const void* da, int ldda, const void* pre, int ldp, void* dpre, int lddp, int R, int H, int Hp, void* stream) {
+    FM_CHECK_ARG(da && pre && dpre, "fm_quick_gelu_bwd: null pointer");
+    FM_CHECK_ARG(R > 0 && H > 0 && Hp >= H && Hp % 4 == 0, "fm_quick_gelu_bwd: R=%d H=%d Hp=%d: positive sizes, Hp >= H a multiple of 4", R, H, Hp);
+    FM_CHECK_ARG(ldda % 4 == 0 && ldp % 4 == 0 && lddp % 4 == 0 && ldda >= Hp && ldp >= Hp && lddp >= Hp,
+                 "fm_quick_gelu_bwd: leading dims %d %d %d must be multiples of 4 and >= Hp=%d", ldda, ldp, lddp, Hp);
+    FM_CHECK_ARG(((((uintptr_t)da) | ((uintptr_t)pre) | ((uintptr_t)dpre)) & 7) == 0, "fm_quick_gelu_bwd: pointers must be 8-byte aligned");
+    hipLaunchKernelGGL(quick_gelu_bwd_kernel<false>, dim3(grid_for((size_t)R * Hp / 4)), dim3(256), 0, (hipStream_t)stream, da, ldda, pre, ldp, dpre, lddp,
+                       R, H, Hp);
+    FM_CHECK_LAUNCH("fm_quick_gelu_bwd");
+    return 0;
+}
+
+extern "C" int fm_quick_gelu_bwd_f32(const void* da, int ldda, const void* pre, int ldp, void* dpre, int lddp, int R, int H, void* stream) {
+    FM_CHECK_ARG(da && pre && dpre, "fm_quick_gelu_bwd_f32: null pointer");
+    FM_CHECK_ARG(R > 0 && H > 0 && ldda >= H && ldp >= H && lddp >= H, "fm_quick_gelu_bwd_f32: R=%d H=%d positive, leading dims %d %d %d >= H", R, H, ldda,
+                 ldp, lddp);
+    hipLaunchKernelGGL(quick_gelu_bwd_kernel<true>, dim3(grid_for((size_t)R * H)), dim3(256), 0, (hipStream_t)stream, da, ldda, pre, ldp, dpre, lddp, R, H, H);
+    FM_CHECK_LAUNCH("fm_quick_gelu_bwd_f32");
+    return 0;
+}
+
+extern "C" int fm_tap_add(void* g, int ldg, void* g_bf, int ldgb, const void* dtap, int ldt, const void* row_scale, int rows_per_sample, int R, int D,
+                          void* stream) {
+    FM_CHECK_ARG(g && dtap, "fm_tap_add: null pointer");
+    FM_CHECK_ARG(R > 0 && D > 0 && D % 4 == 0, "fm_tap_add: R=%d D=%d: positive, D a multiple of 4", R, D);
+    FM_CHECK_ARG(!row_scale || rows_per_sample > 0, "fm_tap_add: rows_per_sample=%d must be positive with row_scale", rows_per_sample);
+    FM_CHECK_ARG(ldg >= D && ldt >= D && ldg % 4 == 0 && ldt % 4 == 0 && (!g_bf || (ldgb >= D && ldgb % 4 == 0)),
+                 "fm_tap_add: leading dims %d %d %d must be multiples of 4 and >= D=%d", ldg, ldt, ldgb, D);
+    FM_CHECK_ARG(((((uintptr_t)g) | ((uintptr_t)dtap)) & 15) == 0 && (((uintptr_t)g_bf) & 7) == 0 && (((uintptr_t)row_scale) & 3) == 0,
+                 "fm_tap_add: g / dtap must be 16-byte aligned, g_bf 8-byte aligned");
+    hipLaunchKernelGGL(tap_add_kernel, dim3(grid_for((size_t)R * D / 4)), dim3(256), 0, (hipStream_t)stream, (float*)g, ldg, (bf16_t*)g_bf, ldgb,
+                       (const float*)dtap, ldt, (const float*)row_scale, row_scale ? rows_per_sample : 1, R, D);
+    FM_CHECK_LAUNCH("fm_tap_add");
     return 0;
 }
 

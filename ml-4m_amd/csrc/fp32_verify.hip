@@ -212,6 +212,7 @@ struct Attn32 {
     int ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, B, H, Nq, Nk, mask_kind, causal, zero_attn;
     float scale;
     const uint8_t* kpad; const int32_t* cs; const int16_t* modq; const int16_t* modk; const uint8_t* dense;
+    float* stat_m; float* stat_l;      // backward only, both or neither: scratch (row max, 1 / row sum) of the ordered dK / dV reduction
 };
 
 __device__ __forceinline__ bool blocked32(const Attn32& a, int b, int q, int k) {
@@ -271,19 +272,50 @@ __global__ __launch_bounds__(64) void attn_f32_kernel(Attn32 a) {
         ds[k] = blocked32(a, b, q, k) ? 0.f : pk * (dp - delta) * a.scale;
     }
     __syncthreads();
+    const bool ordered = a.stat_m != nullptr;              // dK / dV follow in attn_f32_dkv_kernel, which needs this row's max and 1 / sum
+    if (ordered && t == 0) {
+        const size_t si = ((size_t)b * a.H + h) * a.Nq + q;
+        a.stat_m[si] = mx; a.stat_l[si] = inv;
+    }
     float dq = 0.f;
     for (int k = 0; k < a.Nk; ++k) {
         const size_t kr = ((size_t)b * a.Nk + k);
         dq = fmaf(ds[k], a.K[kr * a.ldk + h * 64 + t], dq);
-        unsafeAtomicAdd(a.dK + kr * a.lddk + h * 64 + t, ds[k] * qrow[t]);
-        unsafeAtomicAdd(a.dV + kr * a.lddv + h * 64 + t, p[k] * dorow[t]);
+        if (!ordered) {
+            unsafeAtomicAdd(a.dK + kr * a.lddk + h * 64 + t, ds[k] * qrow[t]);
+            unsafeAtomicAdd(a.dV + kr * a.lddv + h * 64 + t, p[k] * dorow[t]);
+        }
     }
     a.dQ[((size_t)b * a.Nq + q) * a.lddq + h * 64 + t] = dq;
 }
 
+// dK / dV of the backward without atomics: one wavefront per (key row, head, sample), thread t owns dimension t of that row and adds the
+// queries' contributions in query order.  The probability of (q, k) is rebuilt from the row max and 1 / row sum the kernel above left in
+// stat_m / stat_l, delta from the forward's output O:  dK[k] += sum_q ds(q, k) Q[q],  dV[k] += sum_q p(q, k) dO[q].
+__global__ __launch_bounds__(64) void attn_f32_dkv_kernel(Attn32 a) {
+    const int k = blockIdx.x, h = blockIdx.y, b = blockIdx.z, t = threadIdx.x;
+    const size_t kr = (size_t)b * a.Nk + k;
+    const float kv = a.K[kr * a.ldk + h * 64 + t], vv = a.V[kr * a.ldv + h * 64 + t];
+    float dk = 0.f, dv = 0.f;
+    for (int q = 0; q < a.Nq; ++q) {
+        const size_t qr = (size_t)b * a.Nq + q, si = ((size_t)b * a.H + h) * a.Nq + q;
+        const float qv = a.Q[qr * a.ldq + h * 64 + t], dov = a.dO[qr * a.lddo + h * 64 + t], ov = a.O[qr * a.ldo + h * 64 + t];
+        const bool blk = blocked32(a, b, q, k);
+        const float dot = wave_sum(qv * kv);
+        const float s = blk ? NEG_FILL32 : dot * a.scale;
+        const float pk = expf(s - a.stat_m[si]) * a.stat_l[si];
+        const float dp = wave_sum(dov * vv), delta = wave_sum(ov * dov);
+        const float dsk = blk ? 0.f : pk * (dp - delta) * a.scale;
+        dk = fmaf(dsk, qv, dk);
+        dv = fmaf(pk, dov, dv);
+    }
+    a.dK[kr * a.lddk + h * 64 + t] += dk;
+    a.dV[kr * a.lddv + h * 64 + t] += dv;
+}
+
 // ------------------------------------------------------------------------------------------------------------------------------
-// LayerNorm backward with fp32 dy: dx = dres + rstd * (g - mean(g) - xhat * mean(g * xhat)), g = dy * w; dw, db by atomics.
-// One workgroup (256 threads) per row.
+// LayerNorm backward with fp32 dy: dx = dres + rstd * (g - mean(g) - xhat * mean(g * xhat)), g = dy * w.  One workgroup (256 threads) per row.
+// dw, db: colred_f32_kernel below (sums over the rows in a fixed order).
 // ------------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float block_sum256(float v, float* red) {
     v = wave_sum(v);
@@ -295,7 +327,7 @@ __device__ __forceinline__ float block_sum256(float v, float* red) {
 
 __global__ __launch_bounds__(256) void ln_bwd_f32_kernel(const float* dy, int lddy, const int* dy_row_map, const float* x, int ldx, const float* w,
                                                          const float* mean, const float* rstd, const float* dres, float* dx, int lddx,
-                                                         float* dx2, int lddx2, float* dw, float* db, int R, int D) {
+                                                         float* dx2, int lddx2, int R, int D) {
     __shared__ float red[4];
     const int r = blockIdx.x;
     const int sr = dy_row_map ? dy_row_map[r] : r;
@@ -315,8 +347,43 @@ __global__ __launch_bounds__(256) void ln_bwd_f32_kernel(const float* dy, int ld
         if (dres) v += dres[(size_t)r * lddx + c];
         dx[(size_t)r * lddx + c] = v;
         if (dx2) dx2[(size_t)r * lddx2 + c] = v;
-        if (dw) unsafeAtomicAdd(dw + c, dyv * xh);
-        if (db) unsafeAtomicAdd(db + c, dyv);
+    }
+}
+
+// Column reductions over the rows in a FIXED order (no atomics: the same bits on every run).  A workgroup owns 64 columns; its 1024 threads are
+// 64 columns x 16 row groups: group g adds rows g, g + 16, ... in that order, the 16 partial sums meet in LDS and are added in group order.
+//   LN = false: db[n] += sum_r dy[r][n]                                             (fm_colsum_f32)
+//   LN = true:  dw[n] += sum_r dy[sr][n] xhat[r][n],  db[n] += sum_r dy[sr][n]      (fm_layernorm_bwd_f32; sr = dy_row_map[r], < 0: no gradient)
+constexpr int COLRED_GROUPS = 16;
+template <bool LN>
+__global__ __launch_bounds__(64 * COLRED_GROUPS) void colred_f32_kernel(const float* __restrict__ dy, int lddy, const int* __restrict__ dy_row_map,
+                                                                        const float* __restrict__ x, int ldx, const float* __restrict__ mean,
+                                                                        const float* __restrict__ rstd, float* dw, float* db, int R, int N) {
+    __shared__ float pw[COLRED_GROUPS][64], pb[COLRED_GROUPS][64];
+    const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + lane;
+    float sw = 0.f, sb = 0.f;
+    if (c < N) {
+#pragma unroll 4
+        for (int r = g; r < R; r += COLRED_GROUPS) {
+            if constexpr (LN) {
+                const int sr = dy_row_map ? dy_row_map[r] : r;
+                const float dyv = sr >= 0 ? dy[(size_t)sr * lddy + c] : 0.f;
+                sw += dyv * ((x[(size_t)r * ldx + c] - mean[r]) * rstd[r]);
+                sb += dyv;
+            } else {
+                sb += dy[(size_t)r * lddy + c];
+            }
+        }
+    }
+    pw[g][lane] = sw; pb[g][lane] = sb;
+    __syncthreads();
+    if (g == 0 && c < N) {
+        float tw = 0.f, tb = 0.f;
+#pragma unroll
+        for (int k = 0; k < COLRED_GROUPS; ++k) { tw += pw[k][lane]; tb += pb[k][lane]; }
+        if (LN && dw) dw[c] += tw;
+        if (db) db[c] += tb;
     }
 }
 
@@ -361,13 +428,6 @@ __global__ void gelu_bwd_f32_kernel(const float* dh, int lddh, const float* pre,
     const float x = pre[(size_t)r * ldp + c];
     const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752f)), pdf = 0.3989422804014327f * expf(-0.5f * x * x);
     dpre[(size_t)r * lddp + c] = dh[(size_t)r * lddh + c] * (cdf + x * pdf);
-}
-__global__ void colsum_f32_kernel(const float* dy, int ldy, float* db, int R, int N) {
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    if (n >= N) return;
-    float s = 0.f;
-    for (int r = blockIdx.y; r < R; r += gridDim.y) s += dy[(size_t)r * ldy + n];
-    unsafeAtomicAdd(db + n, s);
 }
 
 }  // namespace
@@ -422,8 +482,13 @@ extern "C" int fm_attn_f32_bwd(const fm_attn_args* p, void* stream) {
     Attn32 a{};
     if (int rc = fill32(a, p)) return rc;
     FM_CHECK_ARG(a.dO && a.dQ && a.dK && a.dV, "fm_attn_f32_bwd: null pointer");
+    if (p->stat_m && p->stat_l) { a.stat_m = (float*)p->stat_m; a.stat_l = (float*)p->stat_l; }      // scratch given: dK / dV without atomics
     hipLaunchKernelGGL(attn_f32_kernel<true>, dim3(a.Nq, a.H, a.B), dim3(64), (size_t)a.Nk * 8, (hipStream_t)stream, a);
     FM_CHECK_LAUNCH("fm_attn_f32_bwd");
+    if (a.stat_m) {
+        hipLaunchKernelGGL(attn_f32_dkv_kernel, dim3(a.Nk, a.H, a.B), dim3(64), 0, (hipStream_t)stream, a);
+        FM_CHECK_LAUNCH("fm_attn_f32_bwd");
+    }
     return 0;
 }
 
@@ -431,9 +496,13 @@ extern "C" int fm_layernorm_bwd_f32(const void* dy, int lddy, const int32_t* dy_
                                     const void* rstd, const void* dres, void* dx, int lddx, void* dx2, int lddx2, void* dw, void* db, int R,
                                     int D, void* stream) {
     FM_CHECK_ARG(dy && x && w && mean && rstd && dx && R > 0 && D > 0, "fm_layernorm_bwd_f32: bad argument");
+    if (dw || db) {      // first: it only reads the operands (dx may be the buffer of dy or x)
+        hipLaunchKernelGGL(colred_f32_kernel<true>, dim3((D + 63) / 64), dim3(64 * COLRED_GROUPS), 0, (hipStream_t)stream, (const float*)dy, lddy,
+                           (const int*)dy_row_map, (const float*)x, ldx, (const float*)mean, (const float*)rstd, (float*)dw, (float*)db, R, D);
+        FM_CHECK_LAUNCH("fm_layernorm_bwd_f32");
+    }
     hipLaunchKernelGGL(ln_bwd_f32_kernel, dim3(R), dim3(256), 0, (hipStream_t)stream, (const float*)dy, lddy, dy_row_map, (const float*)x, ldx,
-                       (const float*)w, (const float*)mean, (const float*)rstd, (const float*)dres, (float*)dx, lddx, (float*)dx2, lddx2,
-                       (float*)dw, (float*)db, R, D);
+                       (const float*)w, (const float*)mean, (const float*)rstd, (const float*)dres, (float*)dx, lddx, (float*)dx2, lddx2, R, D);
     FM_CHECK_LAUNCH("fm_layernorm_bwd_f32");
     return 0;
 }
@@ -469,7 +538,8 @@ extern "C" int fm_gelu_bwd_f32(const void* dh, int lddh, const void* pre, int ld
 }
 extern "C" int fm_colsum_f32(const void* dy, int ldy, void* db, int R, int N, void* stream) {
     FM_CHECK_ARG(dy && db && R > 0 && N > 0, "fm_colsum_f32: bad argument");
-    hipLaunchKernelGGL(colsum_f32_kernel, dim3((N + 255) / 256, R < 64 ? R : 64), dim3(256), 0, (hipStream_t)stream, (const float*)dy, ldy, (float*)db, R, N);
+    hipLaunchKernelGGL(colred_f32_kernel<false>, dim3((N + 63) / 64), dim3(64 * COLRED_GROUPS), 0, (hipStream_t)stream, (const float*)dy, ldy, (const int*)nullptr,
+                       (const float*)nullptr, 0, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (float*)db, R, N);
     FM_CHECK_LAUNCH("fm_colsum_f32");
     return 0;
 }

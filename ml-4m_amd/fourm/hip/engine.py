@@ -675,7 +675,7 @@ class FourMEngine:
         else:
             pre = self._buf(sv, tag, "pre", (Rp, self.Hp), bf) if sv is not None else None     # inference: nothing to save
             act = self._buf(sv, tag, "act", (Rp, self.Hp), bf)
-            # ("quick_gelu": CLIP's tower, fourm/utils/clip/model.py - inference only, so pre is never asked for there)
+            # ("quick_gelu": CLIP's tower, fourm/utils/clip/model.py; pre is kept by the saving pass of the perceptual loss, as for "gelu")
             ops.gemm_nt(h, self.w(mlp.fc1.weight), act, epilogue=L.EPI_QUICK_GELU if self.act == "quick_gelu" else L.EPI_GELU, out2=pre, bias=mlp.fc1.bias,
                         M=R, N=self.Hd, K=self.D)
         self._residual(act, mlp.fc2, x_res, x_out, R, self.D, self.Hp, defer)
@@ -955,7 +955,8 @@ class FourMEngine:
         backwards write each residual-stream gradient copy to its own buffer until this point.  The low-rank launches of a wrapped
         Linear (_lora_bwd) only READ those operands; what they write is the dX buffer behind its base GEMM and the adapters' gradients."""
         jobs, self._dw_jobs = self._dw_jobs, None
-        ops.gemm_tn_multi(jobs)
+        if jobs:                                # (a block whose parameters are all frozen queues nothing)
+            ops.gemm_tn_multi(jobs)
 
     def _ln_bwd(self, norm, dy, x, sv, key, g, g_bf, R, dres, dy_row_map=None):
         dw = self._g(norm.weight)
@@ -973,7 +974,7 @@ class FourMEngine:
         # FUSE_ACT_BWD: the activation backward runs in the fc2 dX GEMM epilogue on the saved (g | u) / pre, so
         # d(act) never reaches HBM.  Off by default: even with 16-byte epilogue loads / stores the fused GEMM costs
         # 6.3 ms per 4M-B step against 3.1 + 3.0 ms for the plain GEMM + the coalesced stand-alone kernel.
-        fuse = FUSE_ACT_BWD
+        fuse = FUSE_ACT_BWD and self.act != "quick_gelu"        # (FM_EPI_GELU_BWD is the erf form)
         if not fuse:
             da = ws.get("bwd.da", (Rp, Hp), bf)
             padN = not self.fp32 and Hp != Hd                   # zero rows up to Hp in the weight image: d(act) of the pad columns is 0
@@ -995,6 +996,8 @@ class FourMEngine:
             dpre = ws.get("bwd.dpre", (Rp, Hp), bf)
             if fuse:
                 ops.gemm_nt(g_bf, self.wt(mlp.fc2.weight), dpre, M=R, N=Hd, K=D, epilogue=L.EPI_GELU_BWD, res=sv["pre"])
+            elif self.act == "quick_gelu":      # CLIP's MLP (no fused form: the frozen tower's backward is not the trunk's hot path)
+                ops.quick_gelu_bwd(da, sv["pre"], dpre, Hd, Hp, R=R)
             else:
                 ops.gelu_bwd(da, sv["pre"], dpre, Hd, Hp, R=R)
             self._dW(dpre, sv["h2"], mlp.fc1, R64, n_cols=Hd)

@@ -404,7 +404,7 @@ def attn_bwd(q, k, v, o, do, dq, dk, dv, B, H, Nq, Nk, scale, stat_m, stat_l, *,
     a.dO, a.dQ, a.dK, a.dV = _p(do), _p(dq), _p(dk), _p(dv)
     a.lddo, a.lddq, a.lddk, a.lddv = do.stride(0), dq.stride(0), dk.stride(0), dv.stride(0)
     if q.dtype == torch.float32:
-        dk.zero_(); dv.zero_()                      # the verification kernel accumulates dK / dV with atomics
+        dk.zero_(); dv.zero_()                      # the verification kernel ACCUMULATES dK / dV (in query order with stat_m / stat_l as scratch, else by atomics)
         L.check(L.attn_f32_bwd(C.byref(a), _stream()))
         return
     with _prof("attn_bwd", 10.0 * B * H * Nq * Nk * 64):
@@ -454,6 +454,29 @@ def gelu_bwd(dh, pre, dpre, H, Hp, R=None):
     if dh.dtype == torch.float32:
         return L.check(L.gelu_bwd_f32(_p(dh), _ld(dh), _p(pre), _ld(pre), _p(dpre), _ld(dpre), dh.shape[0] if R is None else R, H, _stream()))
     L.check(L.gelu_bwd(_p(dh), _ld(dh), _p(pre), _ld(pre), _p(dpre), _ld(dpre), dh.shape[0] if R is None else R, H, Hp, _stream()))
+
+
+@_timed("gelu_bwd")
+def quick_gelu_bwd(da, pre, dpre, H, Hp, R=None):
+    """dpre = da * d/du (u sigmoid(1.702 u)) at the saved pre-activation u (CLIP's MLP)."""
+    R = da.shape[0] if R is None else R
+    if da.dtype == torch.float32:
+        return L.check(L.quick_gelu_bwd_f32(_p(da), _ld(da), _p(pre), _ld(pre), _p(dpre), _ld(dpre), R, H, _stream()))
+    L.check(L.quick_gelu_bwd(_p(da), _ld(da), _p(pre), _ld(pre), _p(dpre), _ld(dpre), R, H, Hp, _stream()))
+
+
+def tap_add(g, dtap, g_bf=None, row_scale=None, rows_per_sample=0, R=None):
+    """g[:R] += row_scale[r // rows_per_sample] * dtap[:R] (f32), then g_bf = bf16(g) when a bf16 copy is given."""
+    R = g.shape[0] if R is None else R
+    L.check(L.tap_add(_p(g), _ld(g), _p(g_bf), _ld(g_bf) if g_bf is not None else 0, _p(dtap), _ld(dtap), _p(row_scale), rows_per_sample, R, g.shape[1],
+                      _stream()))
+    return g
+
+
+def feat_distance(pred, tgt, B, T, mode, loss, dpred):
+    """loss[b] += the tap's per-sample feature distance / B; dpred = its gradient with respect to pred (fm_feat_distance)."""
+    L.check(L.feat_distance(_p(pred), _ld(pred), _p(tgt), _ld(tgt), B, T, pred.shape[1], mode, _p(loss), _p(dpred), _ld(dpred), _stream()))
+    return loss
 
 
 def cast_pad(src, dst):

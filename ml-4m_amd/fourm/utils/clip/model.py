@@ -12,7 +12,11 @@ forward is a launch sequence on one MI355X, inference only:
 ``compute_precision`` "bf16" (default) is upstream's autocast arithmetic: bf16 GEMM operands, fp32 accumulation, fp32 residual stream,
 LayerNorm statistics and softmax.  "fp32" runs the same sequence on the fp32 kernels (csrc/fp32_verify.hip): upstream's run without
 autocast.  Every result is fp32.  ``CLIP``, ``ModifiedResNet``, the text tower, ``build_model`` and ``clip.load`` stay upstream's
-(fourm/_upstream.py); ``VisionTransformer.from_upstream(model.visual)`` adopts a loaded tower."""
+(fourm/_upstream.py); ``VisionTransformer.from_upstream(model.visual)`` adopts a loaded tower.
+
+``features`` / ``features_backward`` are the differentiable path of a FROZEN tower: the residual streams after chosen blocks and the gradient of
+anything computed from them with respect to the input image (the perceptual loss of tokenizer training, fourm/vq/percept_losses).  ``forward``
+itself stays inference only, and a tower with trainable parameters is refused by both."""
 import math
 from collections import OrderedDict
 
@@ -21,6 +25,13 @@ import torch.nn.functional as F
 from torch import nn
 
 HEAD_DIM = 64          # the HIP attention kernels are built for this width; CLIP's B/32, B/16 and L/14 towers all have it
+
+
+def affine_fp32(x, scale, shift):
+    """scale[c] * x + shift[c] on (B, C, H, W) with ONE rounding to fp32 per element, differentiable: the value the patch-gather kernel's fused
+    multiply-add gives (fm_vq_patchify_ex), so an affine applied here and one folded into the kernel agree.  The product of two fp32 numbers is
+    exact in float64; the sum is rounded to float64 and then to fp32."""
+    return (x.double() * scale.double().view(1, -1, 1, 1) + shift.double().view(1, -1, 1, 1)).float()
 
 
 class QuickGELU(nn.Module):
@@ -178,30 +189,10 @@ class VisionTransformer(nn.Module):
         from fourm.hip.engine import ru
         from fourm.vq.engine import _blocks_fwd
         f32, bf = torch.float32, torch.bfloat16
-        ws, D, P = eng.ws, self.width, self.patch_size
-        B, C, H, W = x.shape
-        gh, gw = H // P, W // P
-        G = gh * gw
+        ws, D = eng.ws, self.width
+        stream, _, _, (B, G) = self._embed(eng, x, "clip")
         T, Rg = G + 1, B * G
         R = B * T
-        Rp, Rgp, feat = ru(R, 128), ru(Rg, 128), C * P * P
-        x = x.float().contiguous()
-        # conv1 as a GEMM on patch rows 'b c (gh p) (gw q) -> (b gh gw) (c p q)': the column order of the flattened convolution weight
-        if eng.fp32:
-            rows = ws.get("clip.patches32", (Rgp, feat), f32)
-            rows[:Rg].view(B, gh, gw, C, P, P).copy_(x.view(B, C, gh, P, gw, P).permute(0, 2, 4, 1, 3, 5))        # (plumbing)
-            patches = ws.get("clip.proj32", (Rgp, D), f32)
-            ops.gemm_nt(rows, eng.w(self.conv1.weight), patches, epilogue=L.EPI_F32, M=Rg, N=D, K=feat)
-        else:
-            rows = ws.get("clip.patches", (Rgp, ru(feat, 64)), bf)
-            L.check(L.vq_patchify(ops._p(x), ops._p(rows), rows.stride(0), B, C, H, W, P, ops._stream()))
-            patches = ws.get("clip.proj", (Rgp, D), bf)
-            ops.gemm_nt(rows, eng.w(self.conv1.weight), patches, M=Rg, N=D, K=ru(feat, 64))
-        # class token + position table + ln_pre -> the fp32 residual stream
-        pos = self._pos_table(gh, gw, x.device)
-        stream = ws.get("clip.x0", (Rp, D), f32)
-        L.check(L.clip_embed_ln(ops._p(patches), patches.stride(0), 1 if eng.fp32 else 0, ops._p(self.class_embedding), ops._p(pos), ops._p(self.ln_pre.weight),
-                                ops._p(self.ln_pre.bias), ops._p(stream), stream.stride(0), B, G, D, self.ln_pre.eps, ops._stream()))
         stream = _blocks_fwd(eng, self, stream, B, T, None, "clip")
         eng._settle()
         # ln_post on the rows that are returned (the row map drops or picks the class rows), then the projection
@@ -223,6 +214,131 @@ class VisionTransformer(nn.Module):
             ops.gemm_nt(n, eng.wt(self.proj), o16, M=M, N=O, K=ru(D, 64))
             out = o16[:M, :O].float()
         return out if mode == "cls" else out.view(B, M // B, O)
+
+    def _embed(self, eng, x, prefix, scale=None, shift=None):
+        """Images -> the fp32 residual stream in front of block 0 (buffers named under ``prefix``): conv1 as a GEMM on patch rows
+        'b c (gh p) (gw q) -> (b gh gw) (c p q)' (the column order of the flattened convolution weight), then class token + position table +
+        ln_pre.  ``scale`` / ``shift`` (fp32 (3,) device tensors): the per-channel affine scale * x + shift applied while the rows are gathered.
+        Returns (stream, patch-projection rows, position table, (B, G))."""
+        from fourm.hip import _lib as L
+        from fourm.hip import ops
+        from fourm.hip.engine import ru
+        f32, bf = torch.float32, torch.bfloat16
+        ws, D, P = eng.ws, self.width, self.patch_size
+        B, C, H, W = x.shape
+        gh, gw = H // P, W // P
+        G = gh * gw
+        Rg, R = B * G, B * (G + 1)
+        Rp, Rgp, feat = ru(R, 128), ru(Rg, 128), C * P * P
+        x = x.float().contiguous()
+        if eng.fp32:
+            if scale is not None:
+                x = affine_fp32(x, scale, shift)
+            rows = ws.get(prefix + ".patches32", (Rgp, feat), f32)
+            rows[:Rg].view(B, gh, gw, C, P, P).copy_(x.view(B, C, gh, P, gw, P).permute(0, 2, 4, 1, 3, 5))        # (plumbing)
+            patches = ws.get(prefix + ".proj32", (Rgp, D), f32)
+            ops.gemm_nt(rows, eng.w(self.conv1.weight), patches, epilogue=L.EPI_F32, M=Rg, N=D, K=feat)
+        else:
+            rows = ws.get(prefix + ".patches", (Rgp, ru(feat, 64)), bf)
+            if scale is None:
+                L.check(L.vq_patchify(ops._p(x), ops._p(rows), rows.stride(0), B, C, H, W, P, ops._stream()))
+            else:
+                L.check(L.vq_patchify_ex(ops._p(x), None, None, ops._p(scale), ops._p(shift), ops._p(rows), rows.stride(0), B, C, H, W, P, ops._stream()))
+            patches = ws.get(prefix + ".proj", (Rgp, D), bf)
+            ops.gemm_nt(rows, eng.w(self.conv1.weight), patches, M=Rg, N=D, K=ru(feat, 64))
+        # class token + position table + ln_pre -> the fp32 residual stream
+        pos = self._pos_table(gh, gw, x.device)
+        stream = ws.get(prefix + ".x0", (Rp, D), f32)
+        L.check(L.clip_embed_ln(ops._p(patches), patches.stride(0), 1 if eng.fp32 else 0, ops._p(self.class_embedding), ops._p(pos), ops._p(self.ln_pre.weight),
+                                ops._p(self.ln_pre.bias), ops._p(stream), stream.stride(0), B, G, D, self.ln_pre.eps, ops._stream()))
+        return stream, patches, pos, (B, G)
+
+    # ---- the differentiable path of a FROZEN tower: residual streams after some blocks, and the gradient back to the pixels ------------
+    def features(self, x: torch.Tensor, taps, save: bool, scale=None, shift=None):
+        """Residual streams after the blocks in ``taps`` (indices; every token, class token included) for images x (B, 3, H, W): the launch
+        sequence of ``forward`` up to the highest tap, without ln_post or the projection.  Returns ({tap: (B * T, width) fp32 rows}, saved).
+        save=False: the rows are copies and ``saved`` is None.  save=True: the rows are the engine's own buffers and ``saved`` is what
+        ``features_backward`` needs - it lives in the engine's named workspace, so the tower keeps ONE saved pass: the most recent one.
+        ``scale`` / ``shift``: a per-channel affine folded into the patch gather (``features_backward`` then applies ``scale`` on the way out)."""
+        if any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError("the tower's differentiable path is that of a frozen tower (gradient to the input image only): "
+                                      "freeze it with requires_grad_(False)")
+        taps = sorted(set(int(t) for t in taps))
+        if not taps or taps[0] < 0 or taps[-1] >= len(self.blocks):
+            raise ValueError(f"taps {taps}: block indices in range({len(self.blocks)}) expected")
+        if x.dim() != 4 or x.shape[1] != self.conv1.in_channels:
+            raise ValueError(f"expected images (B, {self.conv1.in_channels}, H, W), got {tuple(x.shape)}")
+        P = self.patch_size
+        if x.shape[2] % P or x.shape[3] % P:
+            raise ValueError(f"image size {x.shape[2]}x{x.shape[3]} must be divisible by the patch size {P}")
+        eng = _engine(self)
+        if x.device != eng.device:
+            raise RuntimeError(f"input on {x.device}, model on {eng.device}")
+        from fourm.hip import _lib as L
+        none = dict(mask_kind=L.MASK_NONE)
+        with torch.no_grad():
+            if save:
+                self.__dict__["_feat_saved"] = None                  # (the buffers of an earlier saving pass are about to be rewritten)
+            stream, patches, pos, (B, G) = self._embed(eng, x, "clipf" if save else "clip", scale, shift)
+            T = G + 1
+            R, top, out, layers = B * T, taps[-1], {}, []
+            for i in range(top + 1):
+                sv = {} if save else None
+                nxt = eng.encoder_block_fwd(self.blocks[i], stream, B, T, none, sv, f"clipf{i}" if save else f"clip{i % 2}", defer_out=i < top)
+                layers.append(sv)
+                if i - 1 in taps:                                    # block i's norm1 has written the stream after block i - 1
+                    out[i - 1] = stream[:R] if save else stream[:R].clone()
+                stream = nxt
+            eng._settle()
+            out[top] = stream[:R] if save else stream[:R].clone()
+            saved = None
+            if save:
+                saved = self.__dict__["_feat_saved"] = dict(eng=eng, layers=layers, patches=patches, pos=pos, dims=(B, G, x.shape[2], x.shape[3]),
+                                                            top=top, scale=scale)
+        return out, saved
+
+    def features_backward(self, saved, d_taps, row_scale=None):
+        """Gradient with respect to the images of the ``features(..., save=True)`` pass that returned ``saved``.  d_taps {tap: (>= B * T, width)
+        fp32 gradient rows}, ``row_scale`` (B,) fp32 or None: sample b's rows of every tap gradient are multiplied by row_scale[b] as they
+        enter.  Walks the blocks from the highest tap down (before block i's backward, tap i's gradient is added to the fp32 stream gradient
+        and its bf16 copy refreshed), then the embedding + ln_pre backward, the patch projection and the un-patching.  No parameter
+        gradient is produced."""
+        if saved is None or saved is not self.__dict__.get("_feat_saved") or saved["eng"] is not self.__dict__.get("_hip_engine"):
+            raise RuntimeError("CLIP tower backward: the engine keeps the state of the most recent training forward only "
+                               "(run forward and backward of one batch before the next forward)")
+        self.__dict__["_feat_saved"] = None
+        from fourm.hip import _lib as L
+        from fourm.hip import ops
+        from fourm.hip.engine import ru
+        eng = saved["eng"]
+        f32 = torch.float32
+        ws, D, P = eng.ws, self.width, self.patch_size
+        B, G, H, W = saved["dims"]
+        T, Rg, C = G + 1, B * G, self.conv1.in_channels
+        R, feat = B * T, C * P * P
+        Rp, Rgp = ru(R, 128), ru(Rg, 128)
+        none = dict(mask_kind=L.MASK_NONE)
+        with torch.no_grad():
+            g = ws.get("bwd.clipf.g", (Rp, D), f32)
+            g_bf = ws.get("bwd.clipf.g_bf", (Rp, D), eng.adt)
+            g.zero_()
+            for i in reversed(range(saved["top"] + 1)):
+                if i in d_taps:
+                    ops.tap_add(g, d_taps[i], None if eng.fp32 else g_bf, row_scale, T, R)
+                    if eng.fp32:
+                        g_bf.copy_(g)
+                eng.encoder_block_bwd(self.blocks[i], saved["layers"][i], g, g_bf, B, T, none)
+            patches = saved["patches"]
+            dpat = ws.get("bwd.clipf.dpat", (Rgp, D), eng.adt)
+            L.check(L.clip_embed_ln_bwd(ops._p(g), g.stride(0), ops._p(patches), patches.stride(0), 1 if eng.fp32 else 0, ops._p(saved["pos"]),
+                                        ops._p(self.ln_pre.weight), ops._p(dpat), dpat.stride(0), B, G, D, self.ln_pre.eps, ops._stream()))
+            drows = ws.get("bwd.clipf.drows", (Rgp, feat), f32)
+            ops.gemm_nt(dpat, eng.wt(self.conv1.weight), drows, epilogue=L.EPI_F32, M=Rg, N=feat, K=D)        # d(rows) = d(patches) conv1.weight
+            img = torch.empty(B, C, H, W, dtype=f32, device=g.device)
+            L.check(L.vq_unpatchify(ops._p(drows), drows.stride(0), ops._p(img), B, C, H, W, P, ops._stream()))
+            if saved["scale"] is not None:
+                img *= saved["scale"].view(1, C, 1, 1)
+        return img
 
     def _row_map(self, mode, B, T, device):
         """Destination row of every stream row for ln_post (-1: not normalised into the output)."""
