@@ -38,9 +38,13 @@ enum fm_epilogue {
     FM_EPI_SWIGLU_BWD = 6, /* acc = d(silu(g)*u); res(bf16,(M,2*Hp)) = g|u saved by FM_EPI_SWIGLU;
                               out(bf16,(M,2*Hp)) = dg | du.  Columns [roundup4(N), Hp) of each half are not written */
     FM_EPI_GELU_BWD = 7, /* acc = d(gelu(pre)); res(bf16) = pre saved by FM_EPI_GELU; out(bf16) = d(pre) */
-    FM_EPI_QUICK_GELU = 8 /* CLIP's QuickGELU: pre = bf16(acc + bias); out(bf16) = pre / (1 + exp(-1.702 pre)); out2(bf16, optional) = pre.
+    FM_EPI_QUICK_GELU = 8, /* CLIP's QuickGELU: pre = bf16(acc + bias); out(bf16) = pre / (1 + exp(-1.702 pre)); out2(bf16, optional) = pre.
                              Accepted wherever FM_EPI_GELU is (same kernels, same dispatch) and by the few-row kernel; large |pre| gives
                              +-0 or pre, never NaN */
+    FM_EPI_RELU = 9,      /* out(bf16) = max(bf16(acc + bias), 0).  Implicit convolutions (conv_*) only, never split over K; dense launches are
+                             refused.  fm_gemm_f32 takes it too: out(f32) = max(acc + bias, 0) */
+    FM_EPI_RELU_BWD = 10  /* acc = d(relu(pre)); res(bf16, row stride ldr) = the ReLU output saved by FM_EPI_RELU (or any rows whose sign is
+                             the mask); out(bf16) = res > 0 ? bf16(acc) : 0.  No bias.  Implicit convolutions only; refused by fm_gemm_f32 */
 };
 
 typedef struct fm_gemm_group {  /* one entry per row segment (modality) in grouped mode */
@@ -83,7 +87,8 @@ typedef struct fm_gemm_nt_args {
      * computes out[(b, oy, ox)][n] = sum over tap, c of in[b][oy stride + tap / 3 - 1][ox stride + tap % 3 - 1][c] W[n][tap conv_C + c] (zero
      * padding) on a (conv_Ho, conv_Wo) output grid: M = B conv_Ho conv_Wo, K = 9 conv_C, conv_C % 64 == 0, conv_stride 1 | 2 - exactly
      * fm_unet_im2col + the plain launch (bit-identical), without writing the 9 x expanded rows.  FM_EPI_BF16 (may be split over K like any
-     * small launch) or FM_EPI_F32, dense, no residual / second output. */
+     * small launch) or FM_EPI_F32, dense, no residual / second output; FM_EPI_RELU (bias allowed) and FM_EPI_RELU_BWD (res = the bf16
+     * mask rows, ldr % 4 == 0, ldr >= roundup4(N), res / out 8-byte aligned, no bias), neither ever split over K. */
     int32_t conv_C, conv_H, conv_W, conv_Ho, conv_Wo, conv_stride, conv_up, conv_pad_;
 } fm_gemm_nt_args;
 int fm_gemm_nt(const fm_gemm_nt_args* args, void* stream);
@@ -447,6 +452,49 @@ int fm_clip_embed_ln_bwd(const void* dy, int lddy, const void* patches, int ldp,
                          void* d_patches, int lddp, int B, int G, int D, float eps, void* stream);
 int fm_tap_add(void* g, int ldg, void* g_bf, int ldgb, const void* dtap, int ldt, const void* row_scale, int rows_per_sample, int R, int D,
                void* stream);
+
+/* LPIPS perceptual loss (upstream fourm/vq/percept_losses/lpips.py:96-109, :112-177): a FROZEN VGG16 feature stack tapped after relu1_2,
+ * relu2_2, relu3_3, relu4_3 and relu5_3, forward and the backward down to the pixels (never a dW).  csrc/lpips.hip.  Feature maps are rows
+ * (B * H * W, C) ("NHWC"), bf16 or (is_f32 != 0) f32; the 12 convolutions behind the stem are fm_gemm_nt(conv_*) with FM_EPI_RELU, their
+ * input gradients the same launch on the dgrad weight image with FM_EPI_RELU_BWD (fp32 mode: fm_unet_im2col_f32 + fm_gemm_f32).
+ * Fixed summation orders and no atomics throughout: two runs give the same bits.
+ *
+ * fm_lpips_stem: ScalingLayer + conv1_1 (3 -> 64, 3 x 3, padding 1) + bias + ReLU.  img f32 (B, 3, H, W) contiguous; mul / add f32 (3): the
+ *   ScalingLayer as ONE fp32 multiply-add, s = fma(x, mul[c], add[c]) (mul = 1 / scale, add = -shift / scale); w f32 (64, 27) = conv.weight
+ *   (k = c 9 + ky 3 + kx), bias f32 (64).  The zero padding is applied to s: a tap outside the image contributes 0, not add[c].
+ *   is_f32 == 0: s, w and bias are rounded to bf16, the 27 products are added in fp32 in k order, out(bf16) = max(bf16(acc + bias), 0);
+ *   is_f32 != 0: nothing is rounded, out(f32) = max(acc + bias, 0).  out rows (B * H * W, ldo >= 64), ldo % 8 == 0, 16-byte aligned.
+ * fm_lpips_stem_bwd: the adjoint.  d: the MASKED gradient of conv1_1's pre-activation, rows (B * H * W, ldd) bf16 or f32;
+ *   dimg[b][c][y][x] = ((sum over ky, kx, then n = 0..63, of d[b][y + 1 - ky][x + 1 - kx][n] w[n][c][ky][kx]) * mul[c]) * row_scale[b]
+ *   f32 (B, 3, H, W), every element written once; row_scale f32 (B) = the incoming d / d loss[b] (the whole backward is linear per sample,
+ *   so it is applied once, here), or NULL: 1.  is_f32 == 0 rounds w to bf16 as the forward does.  ldd % 8 == 0, 16-byte aligned d.
+ * fm_maxpool2x2_nhwc: y[b][oy][ox][c] = max of the 2 x 2 window of x (B, H, W, C) -> (B, H / 2, W / 2, C); H, W even, C % 8 == 0,
+ *   ldx / ldy % 8 == 0 and >= C, 16-byte aligned rows.
+ * fm_lpips_distance: pred / tgt rows (B * P, C) of one tap, w f32 (C) = the tap's 1 x 1 lin weights.  Per pixel p^ = p / (|p| + 1e-10), t^
+ *   likewise (upstream's normalize_tensor); loss[b] += (sum over the pixels of sum_c w_c (p^_c - t^_c)^2) / P, all in fp32.  dpred (f32 rows
+ *   (B * P, lddp), or NULL: the no-grad pass) receives d loss[b] / d p = g / (|p| + eps) - p <g, p> / ((|p| + eps)^2 |p|) with
+ *   g_c = 2 w_c (p^_c - t^_c) / P.  Where |p| = 0 the second term, which divides by the norm, is taken as 0 (torch's autograd yields NaN
+ *   there; the ReLU mask of the tap layer zeroes that pixel's gradient anyway, p = 0 meaning every channel is masked).
+ *   One workgroup per (sample, chunk of FM_LPIPS_CHUNK pixels) writes its partial sum to scratch (f32, B * ceil(P / FM_LPIPS_CHUNK) values,
+ *   caller-owned); a second launch adds a sample's partial sums in chunk order onto loss[b].  C % 4 == 0, C <= 512, ldp / ldt / lddp % 4 == 0
+ *   and >= C, 16-byte aligned pointers.
+ * fm_lpips_tap_bwd: the gradient of a layer's pre-activation from what arrives at its ReLU output, rows (B * H * W, C):
+ *     d = [act > 0] (din + dtap + (this position is the FIRST maximum of its 2 x 2 window in scan order (0,0),(0,1),(1,0),(1,1) ? dpool : 0))
+ *   act: the saved ReLU output; din (same type as d, may alias d: the in-place mask), dtap (f32 rows from fm_lpips_distance) and dpool
+ *   (rows (B * H/2 * W/2, C) of d's type: the gradient of the max-pool's output; H, W even) are each optional (NULL).  The first-maximum rule
+ *   is torch's max_pool2d backward; bf16 activations tie often.  Sum in fp32 in the order written, one rounding to d's type.  C % 4 == 0,
+ *   leading dimensions % 4 == 0 and >= C, 16-byte (f32) / 8-byte (bf16) aligned pointers.
+ * Refused (-1) without touching any output: null pointers where one is required, non-positive sizes, the alignment rules above. */
+#define FM_LPIPS_CHUNK 64
+int fm_lpips_stem(const void* img, const void* mul, const void* add, const void* w, const void* bias, void* out, int ldo, int is_f32, int B, int H,
+                  int W, void* stream);
+int fm_lpips_stem_bwd(const void* d, int ldd, int is_f32, const void* w, const void* mul, const void* row_scale, void* dimg, int B, int H, int W,
+                      void* stream);
+int fm_maxpool2x2_nhwc(const void* x, int ldx, void* y, int ldy, int is_f32, int B, int H, int W, int C, void* stream);
+int fm_lpips_distance(const void* pred, int ldp, const void* tgt, int ldt, int is_f32, const void* w, int B, int P, int C, void* loss, void* dpred,
+                      int lddp, void* scratch, void* stream);
+int fm_lpips_tap_bwd(const void* act, int lda, const void* din, int ldi, const void* dtap, int ldt, const void* dpool, int ldp, void* d, int ldd,
+                     int is_f32, int B, int H, int W, int C, void* stream);
 
 /* Low-rank adapters (LoRAWrapper, fourm/models/lora_utils.py:44-81: y = linear(x) + scale * lora_up(lora_down(x))), csrc/lora.hip.
  * P = x down^T (fp32 accumulation over K), y += scale * P up^T in place (fp32 sum, rounded once to y's type), P written to p_out.

@@ -93,6 +93,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(fm_gemm_f32_args a) {
                     *o = qgelu32(v);
                     break;
                 case FM_EPI_TANH: *o = tanhf(v); break;
+                case FM_EPI_RELU: *o = fmaxf(v, 0.f); break;
                 case FM_EPI_RESIDUAL: *o = res[(size_t)m * a.ldr + n] + v; break;
                 case FM_EPI_SWIGLU: {
                     if constexpr (DUAL) {
@@ -195,6 +196,7 @@ __global__ __launch_bounds__(256) void gemm_f32_mfma_kernel(fm_gemm_f32_args a) 
                     float v = acc[i][j][4 * g + e] + (bias ? bias[n + e] : 0.f);
                     float* o = out + (size_t)m * a.ldo + n + e;
                     if (a.epilogue == FM_EPI_TANH) v = tanhf(v);
+                    else if (a.epilogue == FM_EPI_RELU) v = fmaxf(v, 0.f);
                     else if (a.epilogue == FM_EPI_GELU) { if (a.out2) ((float*)a.out2)[(size_t)m * a.ldo2 + n + e] = v; v = gelu32(v); }
                     else if (a.epilogue == FM_EPI_QUICK_GELU) { if (a.out2) ((float*)a.out2)[(size_t)m * a.ldo2 + n + e] = v; v = qgelu32(v); }
                     else if (a.epilogue == FM_EPI_RESIDUAL || (a.epilogue == FM_EPI_F32 && res)) v += res[(size_t)m * a.ldr + n + e];
@@ -436,7 +438,7 @@ __global__ void gelu_bwd_f32_kernel(const float* dh, int lddh, const float* pre,
 extern "C" int fm_gemm_f32(const fm_gemm_f32_args* p, void* stream) {
     FM_CHECK_ARG(p && p->X && (p->W || p->groups) && (p->out || p->seg_start), "fm_gemm_f32: null pointer");
     FM_CHECK_ARG(p->M > 0 || p->seg_start, "fm_gemm_f32: bad shape");
-    FM_CHECK_ARG(p->epilogue != FM_EPI_SWIGLU_BWD && p->epilogue != FM_EPI_GELU_BWD, "fm_gemm_f32: activation-backward epilogues are separate kernels here");
+    FM_CHECK_ARG(p->epilogue != FM_EPI_SWIGLU_BWD && p->epilogue != FM_EPI_GELU_BWD && p->epilogue != FM_EPI_RELU_BWD, "fm_gemm_f32: activation-backward epilogues are separate kernels here");
     // accumulate adds the plain fp32 result to out; an activation or residual epilogue has no accumulating form (the two kernels
     // below would disagree on it), so the combination is refused rather than given a meaning that depends on operand alignment
     FM_CHECK_ARG(!p->accumulate || p->epilogue == FM_EPI_F32 || p->epilogue == FM_EPI_BF16,

@@ -430,7 +430,7 @@ __global__ __launch_bounds__(WW * WX * 64) void gemm_nt_kernel(NTArgs a) {
                     }
                 }
             }
-        } else if constexpr (EPI == EPI_BF16 || is_gelu_like<EPI> || EPI == EPI_TANH) {
+        } else if constexpr (EPI == EPI_BF16 || is_gelu_like<EPI> || EPI == EPI_TANH || EPI == EPI_RELU) {
             bf16_t* orow = (bf16_t*)a.out + (size_t)m * a.ldo;
             bf16_t* prow = (is_gelu_like<EPI> && a.out2) ? (bf16_t*)a.out2 + (size_t)m * a.ldo2 : nullptr;
             const bool wide = ((N | a.ldo | (prow ? a.ldo2 : 0)) & 7) == 0 && (((uintptr_t)a.out | (uintptr_t)(prow ? a.out2 : nullptr)) & 15) == 0;
@@ -455,6 +455,9 @@ __global__ __launch_bounds__(WW * WX * 64) void gemm_nt_kernel(NTArgs a) {
                     } else if constexpr (EPI == EPI_TANH) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) v[e] = tanhf(bfround(v[e]));
+                    } else if constexpr (EPI == EPI_RELU) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) v[e] = fmaxf(bfround(v[e]), 0.f);
                     }
                     po[g] = make_uint2(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]));
                 }
@@ -468,7 +471,8 @@ __global__ __launch_bounds__(WW * WX * 64) void gemm_nt_kernel(NTArgs a) {
                     }
                 }
             }
-        } else if constexpr (EPI == EPI_SWIGLU_BWD || EPI == EPI_GELU_BWD) {
+        } else if constexpr (EPI == EPI_SWIGLU_BWD || EPI == EPI_GELU_BWD || EPI == EPI_RELU_BWD) {
+            // (EPI_RELU_BWD: res = the saved bf16 ReLU output of the layer below, out = res > 0 ? bf16(acc) : 0 - the frozen VGG16 of the LPIPS loss)
             // acc = d(act); res = saved (g | u) or pre-activation (bf16); out = (dg | du) or d(pre) (bf16)
             // (GatedMlp fm_utils.py:142-144 / Mlp :121-126).  16-byte loads and stores, see load/store_bf16_groups.
             const bf16_t* srow = (const bf16_t*)a.res + (size_t)m * a.ldr;
@@ -508,6 +512,9 @@ __global__ __launch_bounds__(WW * WX * 64) void gemm_nt_kernel(NTArgs a) {
                             r1[e] = live ? ds * (sg * (1.0f + xv[e] * (1.0f - sg))) : 0.f;
                         }
                         o2[i][g] = make_uint2(pack2bf(r2[0], r2[1]), pack2bf(r2[2], r2[3]));
+                    } else if constexpr (EPI == EPI_RELU_BWD) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) r1[e] = (n + e < N && xv[e] > 0.f) ? acc[i][j][4 * g + e] : 0.f;
                     } else {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
@@ -1286,6 +1293,8 @@ extern "C" int fm_gemm_nt(const fm_gemm_nt_args* p, void* stream) {
     const bool fixed = p->fixed_tiling != 0;      // one kernel, one tile configuration: none of the shape-dependent routes below
     FM_CHECK_ARG(!fixed || (!grouped && !p->m_dev && !p->row0_dev && p->conv_C == 0), "fm_gemm_nt: fixed_tiling is for dense launches (no groups, device-side rows or conv_*)");
     a.fixed_tiling = fixed ? 1 : 0;
+    FM_CHECK_ARG(!(p->epilogue == FM_EPI_RELU || p->epilogue == FM_EPI_RELU_BWD) || (p->conv_C > 0 && !grouped && !p->m_dev && !p->row0_dev),
+                 "fm_gemm_nt: FM_EPI_RELU / FM_EPI_RELU_BWD belong to the implicit convolution (conv_*), not to dense launches");
     if (p->m_dev || p->row0_dev) {            // row range in device memory (one dense launch per modality head): gemm_nt3 only
         FM_CHECK_ARG(p->m_dev && p->row0_dev && !grouped, "fm_gemm_nt: m_dev and row0_dev go together (dense launches only)");
         const int r = fm_launch_nt3(a, p->epilogue, g_lab[2] ? g_lab[2] : 3, s);
@@ -1303,12 +1312,25 @@ extern "C" int fm_gemm_nt(const fm_gemm_nt_args* p, void* stream) {
     }
     a.conv_C = p->conv_C; a.conv_H = p->conv_H; a.conv_W = p->conv_W; a.conv_Ho = p->conv_Ho; a.conv_Wo = p->conv_Wo; a.conv_stride = p->conv_stride; a.conv_up = p->conv_up;
     if (p->conv_C > 0) {          // implicit 3 x 3 convolution: the gathering instantiation of the 128 x 128 kernel, split over K when the grid is small
-        FM_CHECK_ARG(!grouped && !p->m_dev && !p->out2 && !p->res && (p->epilogue == FM_EPI_BF16 || p->epilogue == FM_EPI_F32), "fm_gemm_nt (conv): dense FM_EPI_BF16 / FM_EPI_F32 only");
+        const bool relu_bwd = p->epilogue == FM_EPI_RELU_BWD;
+        FM_CHECK_ARG(!grouped && !p->m_dev && !p->out2 && (relu_bwd || !p->res) &&
+                     (p->epilogue == FM_EPI_BF16 || p->epilogue == FM_EPI_F32 || p->epilogue == FM_EPI_RELU || relu_bwd),
+                     "fm_gemm_nt (conv): dense FM_EPI_BF16 / FM_EPI_F32 / FM_EPI_RELU / FM_EPI_RELU_BWD only, no second output, res with FM_EPI_RELU_BWD only");
+        FM_CHECK_ARG(!relu_bwd || (p->res && !p->bias && p->ldr % 4 == 0 && p->ldr >= (p->N + 3) / 4 * 4 && (((uintptr_t)p->res | (uintptr_t)p->out) & 7) == 0),
+                     "fm_gemm_nt (conv): FM_EPI_RELU_BWD needs res = the saved bf16 activation (ldr %% 4 == 0, ldr >= roundup4(N), 8-byte aligned res / out) and no bias");
         FM_CHECK_ARG(p->conv_C % 64 == 0 && p->K == 9 * p->conv_C && (p->conv_stride == 1 || p->conv_stride == 2) && (p->conv_up == 0 || p->conv_up == 1) &&
                      p->conv_H > 0 && p->conv_W > 0 && p->conv_Ho > 0 && p->conv_Wo > 0 && p->M % (p->conv_Ho * p->conv_Wo) == 0,
                      "fm_gemm_nt (conv): C=%d K=%d stride=%d up=%d grid %dx%d -> %dx%d M=%d", p->conv_C, p->K, p->conv_stride, p->conv_up, p->conv_H, p->conv_W, p->conv_Ho, p->conv_Wo, p->M);
         FM_CHECK_ARG(p->conv_Ho == (p->conv_H + 2 - 3) / p->conv_stride + 1 && p->conv_Wo == (p->conv_W + 2 - 3) / p->conv_stride + 1, "fm_gemm_nt (conv): output grid does not match the input grid");
         if (p->epilogue == FM_EPI_F32) return launch_nt_cfg<128, 128, 2, 2, 64, 3, EPI_F32, false, false, false, true>(a, max_n, s);
+        if (p->epilogue == FM_EPI_RELU) {          // (never split over K: the reduction pass has no activation)
+            if (g_lab[10]) return launch_nt_cfg<128, 128, 2, 2, 32, 3, EPI_RELU, false, false, false, true>(a, max_n, s);
+            return launch_nt_cfg<128, 128, 2, 2, 64, 3, EPI_RELU, false, false, false, true>(a, max_n, s);
+        }
+        if (relu_bwd) {
+            if (g_lab[10]) return launch_nt_cfg<128, 128, 2, 2, 32, 3, EPI_RELU_BWD, false, false, false, true>(a, max_n, s);
+            return launch_nt_cfg<128, 128, 2, 2, 64, 3, EPI_RELU_BWD, false, false, false, true>(a, max_n, s);
+        }
         const int cus = n_compute_units();
         const long t128 = (long)((p->M + 127) / 128) * ((p->N + 127) / 128);
         const int kt = p->K / 64;

@@ -6,7 +6,8 @@
 namespace fmk {
 
 enum { EPI_BF16 = FM_EPI_BF16, EPI_GELU = FM_EPI_GELU, EPI_RES = FM_EPI_RESIDUAL, EPI_SWIGLU = FM_EPI_SWIGLU,
-       EPI_F32 = FM_EPI_F32, EPI_TANH = FM_EPI_TANH, EPI_SWIGLU_BWD = FM_EPI_SWIGLU_BWD, EPI_GELU_BWD = FM_EPI_GELU_BWD, EPI_QGELU = FM_EPI_QUICK_GELU };
+       EPI_F32 = FM_EPI_F32, EPI_TANH = FM_EPI_TANH, EPI_SWIGLU_BWD = FM_EPI_SWIGLU_BWD, EPI_GELU_BWD = FM_EPI_GELU_BWD, EPI_QGELU = FM_EPI_QUICK_GELU,
+       EPI_RELU = FM_EPI_RELU, EPI_RELU_BWD = FM_EPI_RELU_BWD };
 
 struct NTArgs {
     const bf16_t* W; const bf16_t* W2; const bf16_t* X;

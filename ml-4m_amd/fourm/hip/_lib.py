@@ -35,6 +35,7 @@ vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 # enums (keep in sync with the header; tests/test_model_cpu.py::test_ctypes_mirrors_match_the_header_layout cross-checks them, the struct layouts and the prototypes against the header)
 EPI_BF16, EPI_GELU, EPI_RESIDUAL, EPI_SWIGLU, EPI_F32, EPI_TANH, EPI_SWIGLU_BWD, EPI_GELU_BWD, EPI_QUICK_GELU = 0, 1, 2, 3, 4, 5, 6, 7, 8
+EPI_RELU, EPI_RELU_BWD = 9, 10          # implicit convolutions only (the frozen VGG16 of the LPIPS loss)
 MASK_NONE, MASK_KEYPAD, MASK_DECODER, MASK_DENSE = 0, 1, 2, 3
 KIND_TOK, KIND_PATCH, KIND_SEQ, KIND_SEQ_EMB = 0, 1, 2, 3
 LOSS_MOD, LOSS_TOKEN = 0, 1
@@ -273,7 +274,14 @@ quick_gelu_bwd = _sig("fm_quick_gelu_bwd", vp, i32, vp, i32, vp, i32, i32, i32, 
 quick_gelu_bwd_f32 = _sig("fm_quick_gelu_bwd_f32", vp, i32, vp, i32, vp, i32, i32, i32, vp)
 clip_embed_ln_bwd = _sig("fm_clip_embed_ln_bwd", vp, i32, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, f32, vp)
 tap_add = _sig("fm_tap_add", vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, vp)
-EXPORTS = ["fm_feat_distance", "fm_quick_gelu_bwd", "fm_quick_gelu_bwd_f32", "fm_clip_embed_ln_bwd", "fm_tap_add", "fm_clip_embed_ln", "fm_attn_decode", "fm_vit_patch_rows", "fm_vit_emb_rows", "fm_vit_colsum", "fm_lora_apply", "fm_lora_grad", "fm_vq_assign_wide", "fm_memcodes_assign", "fm_convnext_block", "fm_split3_bf16", "fm_unet_im2col", "fm_groupnorm_nhwc", "fm_add_bf16", "fm_silu_f32_to_bf16", "fm_timestep_embedding", "fm_unet_attention", "fm_diffusion_x0", "fm_quantile_abs",
+# LPIPS perceptual loss (csrc/lpips.hip)
+LPIPS_CHUNK = 64      # FM_LPIPS_CHUNK
+lpips_stem = _sig("fm_lpips_stem", vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp)
+lpips_stem_bwd = _sig("fm_lpips_stem_bwd", vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp)
+maxpool2x2_nhwc = _sig("fm_maxpool2x2_nhwc", vp, i32, vp, i32, i32, i32, i32, i32, i32, vp)
+lpips_distance = _sig("fm_lpips_distance", vp, i32, vp, i32, i32, vp, i32, i32, i32, vp, vp, i32, vp, vp)
+lpips_tap_bwd = _sig("fm_lpips_tap_bwd", vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp)
+EXPORTS = ["fm_lpips_stem", "fm_lpips_stem_bwd", "fm_maxpool2x2_nhwc", "fm_lpips_distance", "fm_lpips_tap_bwd", "fm_feat_distance", "fm_quick_gelu_bwd", "fm_quick_gelu_bwd_f32", "fm_clip_embed_ln_bwd", "fm_tap_add", "fm_clip_embed_ln", "fm_attn_decode", "fm_vit_patch_rows", "fm_vit_emb_rows", "fm_vit_colsum", "fm_lora_apply", "fm_lora_grad", "fm_vq_assign_wide", "fm_memcodes_assign", "fm_convnext_block", "fm_split3_bf16", "fm_unet_im2col", "fm_groupnorm_nhwc", "fm_add_bf16", "fm_silu_f32_to_bf16", "fm_timestep_embedding", "fm_unet_attention", "fm_diffusion_x0", "fm_quantile_abs",
            "fm_diffusion_step", "fm_unpack_image_u8", "fm_unpack_ids_u16", "fm_unpack_mask_bits", "fm_decoder_attention_from_target", "fm_guidance_combine", "fm_image_mask", "fm_token_budgets", "fm_span_mask", "fm_vq_code_stats", "fm_vq_ema_update", "fm_vq_code_bias", "fm_vq_assign_bias", "fm_vq_code_stats_raw", "fm_vq_ema_update_euclid", "fm_vq_unpatchify", "fm_vq_latent_grad", "fm_tanh_bwd_f32", "fm_embed_rows_f32", "fm_vq_patchify_ex", "fm_vq_cls_emb_bwd", "fm_vq_latent_grad_normalized", "fm_abi_version", "fm_last_error", "fm_gemm_nt", "fm_set_gemm_nt_config", "fm_get_gemm_nt_config", "fm_set_reserved_cus", "fm_get_reserved_cus", "fm_bf16_to_f32_scaled", "fm_add_bf16_f32", "fm_scale_rows_bf16", "fm_gemm_tn", "fm_gemm_tn_multi", "fm_set_gemm_tn_config", "fm_get_gemm_tn_config", "fm_set_tn_transpose_read",
            "fm_get_tn_transpose_read", "fm_layernorm_fwd", "fm_layernorm_fwd_res", "fm_layernorm_bwd", "fm_layernorm_bwd_h", "fm_headnorm_fwd", "fm_headnorm_bwd", "fm_attn_fwd", "fm_attn_bwd",
            "fm_set_attn_transpose_read", "fm_get_attn_transpose_read", "fm_select_embed", "fm_embed_bwd",

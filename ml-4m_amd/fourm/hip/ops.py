@@ -479,6 +479,62 @@ def feat_distance(pred, tgt, B, T, mode, loss, dpred):
     return loss
 
 
+# ---- LPIPS perceptual loss (csrc/lpips.hip): rows are bf16 or f32, the dtype of the row tensor selects the kernel ----------------------
+def _is_f32(t):
+    if t.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"feature rows are bf16 or f32, got {t.dtype}")
+    return 1 if t.dtype == torch.float32 else 0
+
+
+def lpips_stem(img, mul, add, w, bias, out, B, H, W):
+    """out rows (B H W, 64) = relu(conv1_1(fma(img, mul, add)) + bias): ScalingLayer + the 3 -> 64 convolution (fm_lpips_stem)."""
+    esz = out.element_size()
+    with _prof("lpips_stem", 2.0 * B * H * W * 64 * 27, B * H * W * (12.0 + 64 * esz), tag=f"B{B} {H}x{W}"):
+        L.check(L.lpips_stem(_p(img), _p(mul), _p(add), _p(w), _p(bias), _p(out), _ld(out), _is_f32(out), B, H, W, _stream()))
+    return out
+
+
+def lpips_stem_bwd(d, w, mul, row_scale, dimg, B, H, W):
+    """dimg (B, 3, H, W) f32 = conv1_1^T(d) * mul[c] * row_scale[b] from the masked pre-activation gradient rows d (fm_lpips_stem_bwd)."""
+    with _prof("lpips_stem_bwd", 2.0 * B * H * W * 64 * 27, B * H * W * (12.0 + 64 * d.element_size()), tag=f"B{B} {H}x{W}"):
+        L.check(L.lpips_stem_bwd(_p(d), _ld(d), _is_f32(d), _p(w), _p(mul), _p(row_scale), _p(dimg), B, H, W, _stream()))
+    return dimg
+
+
+def maxpool2x2_nhwc(x, y, B, H, W, C):
+    """y rows (B H/2 W/2, C) = the 2 x 2 max-pool of x rows (B H W, C) (fm_maxpool2x2_nhwc)."""
+    with _prof("maxpool2x2_nhwc", 0.0, 1.25 * B * H * W * C * x.element_size(), tag=f"B{B} {H}x{W} C{C}"):
+        L.check(L.maxpool2x2_nhwc(_p(x), _ld(x), _p(y), _ld(y), _is_f32(x), B, H, W, C, _stream()))
+    return y
+
+
+def lpips_distance_scratch(B, P):
+    """Number of f32 values fm_lpips_distance needs as scratch."""
+    return B * ((P + L.LPIPS_CHUNK - 1) // L.LPIPS_CHUNK)
+
+
+def lpips_distance(pred, tgt, w, B, P, loss, dpred, scratch):
+    """loss[b] += mean over the P pixels of sum_c w_c (p^ - t^)^2; dpred (f32 rows or None) = its gradient with respect to pred."""
+    C_ = pred.shape[1]
+    assert scratch.dtype == torch.float32 and scratch.numel() >= lpips_distance_scratch(B, P) and _is_f32(pred) == _is_f32(tgt)
+    with _prof("lpips_distance", 0.0, B * P * C_ * (2.0 * pred.element_size() + (4.0 if dpred is not None else 0.0)), tag=f"B{B} P{P} C{C_}"):
+        L.check(L.lpips_distance(_p(pred), _ld(pred), _p(tgt), _ld(tgt), _is_f32(pred), _p(w), B, P, C_, _p(loss), _p(dpred),
+                                 _ld(dpred) if dpred is not None else 0, _p(scratch), _stream()))
+    return loss
+
+
+def lpips_tap_bwd(act, d, B, H, W, din=None, dtap=None, dpool=None):
+    """d = [act > 0] (din + dtap + dpool routed to the first maximum of each 2 x 2 window); din may be d itself (fm_lpips_tap_bwd)."""
+    C_ = act.shape[1]
+    f = _is_f32(act)
+    assert _is_f32(d) == f and (din is None or _is_f32(din) == f) and (dpool is None or _is_f32(dpool) == f) and (dtap is None or dtap.dtype == torch.float32)
+    n_in = (din is not None) + (dpool is not None) * 0.25
+    with _prof("lpips_tap_bwd", 0.0, B * H * W * C_ * ((2.0 + n_in) * act.element_size() + (4.0 if dtap is not None else 0.0)), tag=f"B{B} {H}x{W} C{C_}"):
+        L.check(L.lpips_tap_bwd(_p(act), _ld(act), _p(din), _ld(din) if din is not None else 0, _p(dtap), _ld(dtap) if dtap is not None else 0,
+                                _p(dpool), _ld(dpool) if dpool is not None else 0, _p(d), _ld(d), f, B, H, W, C_, _stream()))
+    return d
+
+
 def cast_pad(src, dst):
     """dst (rows, ld>=cols) bf16 <- src (rows, cols) f32, padding zeroed."""
     s2 = src.reshape(src.shape[0], -1)

@@ -11,7 +11,7 @@ image, compared token by token.  The gradient flows through the tower back to th
     projection transposed; fm_vq_unpatchify.
 
 Not here: fetching or converting timm checkpoints (build the tower from an OpenAI CLIP state dict: ``fourm.utils.clip.model.build_visual``),
-LPIPS, DINOv2 or other feature networks, a trainable tower, resizing to the tower's input size."""
+DINOv2 or other feature networks, a trainable tower, resizing to the tower's input size (LPIPS: lpips_loss.py)."""
 import torch
 from torch import nn
 
