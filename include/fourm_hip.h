@@ -837,6 +837,56 @@ int fm_quantile_abs(const void* x, int B, int64_t n, float q, void* out, void* s
 int fm_diffusion_step(const void* x0, const void* quantile, float sample_max_value, float clip_range, const void* sample, const void* model_output,
                       const void* noise, float k0, float k1, float k2, float k3, void* out, void* x0_out, int B, int64_t per_sample, void* stream);
 
+/* Tokenizer training objective (csrc/train_objective.hip): what a tokenizer training step does besides VQVAE.forward / backward and the
+ * perceptual losses.  fp32 throughout; compiled without fused multiply-adds.  No floating-point atomics: every reduction is per-workgroup
+ * partial sums in caller-owned scratch, added in a fixed order - two calls on the same inputs give the same bits.  No input value is ever
+ * used as an index without a range check.
+ *
+ * fm_reconst_loss: upstream's compute_reconst_loss (run_training_vqvae.py:961-1003).  x f32 (B, C, HW) contiguous; target of the same shape,
+ *   except FM_LOSS_CE_INDEX: int64 class indices (B, HW), x holding C = K class scores per pixel.  loss[0] = the scalar loss; grad (f32, x's
+ *   shape, or NULL) = d loss / d x, written in the same launch that writes the loss partials.  scratch: fm_reconst_loss_scratch(...) f32
+ *   values (that function returns the count, or -1).  Two launches (main, fixed-order sum); the index cross-entropy counts its valid pixels
+ *   first (integer atomics), two launches more.
+ *     MSE / L1 / SMOOTH_L1 (beta = 1): mean over all elements; d |d| / d d = 0 at d = 0.
+ *     CE_INDEX: F.cross_entropy over the strided class axis, ignore_index = -100, mean over the pixels whose label is not -100 (none: nan).
+ *       A label outside [0, K) other than -100 makes that pixel's loss and gradient NaN.
+ *     BCE: s = sigmoid(x); F.cross_entropy of the 2 C "logits" [s, 1 - s] against the probabilities q = [t, 1 - t] per pixel (a softmax over
+ *       probabilities, upstream's formulation; sum q = C): d / d z_k = (C p_k - q_k) / (B HW), chained through both occurrences of s_c.
+ *     COSINE: 1 - mean over (b, c) of the cosine similarity along HW;  COSINE_1D: 1 - mean over (b, hw) of the similarity along C.
+ *       cos = <x, t> / (max(|x|, 1e-8) max(|t|, 1e-8)); d cos / d x = t / (|x|' |t|') - cos x / (|x|' |x|), the second term 0 where |x| = 0.
+ * fm_scale_f32: x[i] *= scale[0] (scale: one f32 in DEVICE memory) - the loss's backward; nothing is read or written when scale[0] is exactly 1.
+ * fm_mask_out_samples: upstream's mask_out_samples (:857-878).  clean f32 (B, C, HW), valid uint8 / bool (B, HW), out f32 (B, C + 1, HW):
+ *   where valid is 0 clean is overwritten IN PLACE with mask_value; out = [clean after that | valid * 2 - 1].
+ * fm_ema_update: ModelEma.update (fourm/utils/timm/model_ema.py:70-81) over a job list in ONE launch: for every element of every job
+ *   ema = fadd(fmul(ema, decay), fmul(one_minus_decay, model)), each operation rounded to fp32 separately (torch's three kernels).  jobs: a
+ *   DEVICE array of n_jobs fm_ema_job sorted by first_chunk, job i covering workgroups [first_chunk, first_chunk + ceil(n / FM_EMA_CHUNK));
+ *   chunks = their total.  Pointers 4-byte aligned (16-byte aligned pairs take 16-byte accesses).
+ * fm_diffusion_pair: noisy = fadd(fmul(sa, clean), fmul(ss, noise)) and, unless velocity is NULL, velocity = fsub(fmul(sa, noise),
+ *   fmul(ss, clean)) with sa = sqrt_alpha[timesteps[b]], ss = sqrt_sigma[timesteps[b]] gathered on the device (tables f32 (T), timesteps
+ *   int64 (B)): the schedulers' add_noise / get_velocity, clean and noise read once.  A timestep outside [0, T) yields NaN.  B <= 65535.
+ * fm_token_usage: counts[w] (int32) = the number of distinct values in tokens[w * window, (w + 1) * window), tokens int16 / int32 / int64
+ *   (elem_size 2 / 4 / 8) in [0, K), K <= FM_TOKEN_USAGE_MAX_K: a K-bit bitmap in LDS per window (integer atomicOr), then its population
+ *   count.  bad[0] (int32) = the number of tokens outside [0, K); they are not counted.
+ * Refused (-1) without touching any output: null pointers where one is required, non-positive sizes, misaligned pointers, the limits above. */
+enum { FM_LOSS_MSE = 0, FM_LOSS_L1 = 1, FM_LOSS_SMOOTH_L1 = 2, FM_LOSS_CE_INDEX = 3, FM_LOSS_BCE = 4, FM_LOSS_COSINE = 5, FM_LOSS_COSINE_1D = 6 };
+#define FM_RECONST_CHUNK 4096
+#define FM_EMA_CHUNK 4096
+#define FM_TOKEN_USAGE_MAX_K (1 << 20)
+typedef struct fm_ema_job {
+    void* ema;
+    const void* model;
+    int64_t n;
+    int64_t first_chunk;
+} fm_ema_job;
+int fm_reconst_loss_scratch(int mode, int B, int C, int64_t HW);
+int fm_reconst_loss(const void* x, const void* target, int mode, int B, int C, int64_t HW, void* grad, void* scratch, void* loss, void* stream);
+int fm_scale_f32(void* x, const void* scale, int64_t n, void* stream);
+int fm_mask_out_samples(void* clean, const void* valid, float mask_value, void* out, int B, int C, int64_t HW, void* stream);
+int fm_ema_update(const void* jobs, int n_jobs, int64_t chunks, float decay, float one_minus_decay, void* stream);
+int fm_diffusion_pair(const void* clean, const void* noise, const void* timesteps, const void* sqrt_alpha, const void* sqrt_sigma, int T, void* noisy,
+                      void* velocity, int B, int64_t per_sample, void* stream);
+int fm_token_usage(const void* tokens, int elem_size, int64_t n_windows, int64_t window, int K, void* counts, void* bad, void* stream);
+
 /* ---- lab (not part of the drop-in surface) ------------------------------------------------------------------------------------------
  * Experiment knobs of the GEMM kernels, used by tools/gemm_lab.cpp, the Python tools and the FOURM_NT3_LAB environment switch only: key 0 / 1
  * staggered workgroup start (groups, step), 2 gemm_nt3 mode override, 3 gemm_nt3 ablation flags (gemm_args.h NTArgs::lab), others reserved.

@@ -146,6 +146,10 @@ class EmbedBwdDesc(C.Structure):
                 ("n_mods", i32), ("batch", i32), ("dim", i32), ("Nt", i32), ("lddx", i32), ("is_decoder", i32)]
 
 
+class EmaJob(C.Structure):
+    _fields_ = [("ema", vp), ("model", vp), ("n", i64), ("first_chunk", i64)]
+
+
 def _sig(name, *argtypes):
     fn = getattr(lib, name)
     fn.argtypes = list(argtypes)
@@ -281,7 +285,17 @@ lpips_stem_bwd = _sig("fm_lpips_stem_bwd", vp, i32, i32, vp, vp, vp, vp, i32, i3
 maxpool2x2_nhwc = _sig("fm_maxpool2x2_nhwc", vp, i32, vp, i32, i32, i32, i32, i32, i32, vp)
 lpips_distance = _sig("fm_lpips_distance", vp, i32, vp, i32, i32, vp, i32, i32, i32, vp, vp, i32, vp, vp)
 lpips_tap_bwd = _sig("fm_lpips_tap_bwd", vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp)
-EXPORTS = ["fm_lpips_stem", "fm_lpips_stem_bwd", "fm_maxpool2x2_nhwc", "fm_lpips_distance", "fm_lpips_tap_bwd", "fm_feat_distance", "fm_quick_gelu_bwd", "fm_quick_gelu_bwd_f32", "fm_clip_embed_ln_bwd", "fm_tap_add", "fm_clip_embed_ln", "fm_attn_decode", "fm_vit_patch_rows", "fm_vit_emb_rows", "fm_vit_colsum", "fm_lora_apply", "fm_lora_grad", "fm_vq_assign_wide", "fm_memcodes_assign", "fm_convnext_block", "fm_split3_bf16", "fm_unet_im2col", "fm_groupnorm_nhwc", "fm_add_bf16", "fm_silu_f32_to_bf16", "fm_timestep_embedding", "fm_unet_attention", "fm_diffusion_x0", "fm_quantile_abs",
+# tokenizer training objective (csrc/train_objective.hip)
+LOSS_MSE, LOSS_L1, LOSS_SMOOTH_L1, LOSS_CE_INDEX, LOSS_BCE, LOSS_COSINE, LOSS_COSINE_1D = 0, 1, 2, 3, 4, 5, 6      # FM_LOSS_*
+RECONST_CHUNK, EMA_CHUNK, TOKEN_USAGE_MAX_K = 4096, 4096, 1 << 20      # FM_RECONST_CHUNK, FM_EMA_CHUNK, FM_TOKEN_USAGE_MAX_K
+reconst_loss_scratch = _sig("fm_reconst_loss_scratch", i32, i32, i32, i64)
+reconst_loss = _sig("fm_reconst_loss", vp, vp, i32, i32, i32, i64, vp, vp, vp, vp)
+scale_f32 = _sig("fm_scale_f32", vp, vp, i64, vp)
+mask_out_samples = _sig("fm_mask_out_samples", vp, vp, f32, vp, i32, i32, i64, vp)
+ema_update = _sig("fm_ema_update", vp, i32, i64, f32, f32, vp)
+diffusion_pair = _sig("fm_diffusion_pair", vp, vp, vp, vp, vp, i32, vp, vp, i32, i64, vp)
+token_usage = _sig("fm_token_usage", vp, i32, i64, i64, i32, vp, vp, vp)
+EXPORTS = ["fm_reconst_loss_scratch", "fm_reconst_loss", "fm_scale_f32", "fm_mask_out_samples", "fm_ema_update", "fm_diffusion_pair", "fm_token_usage", "fm_lpips_stem", "fm_lpips_stem_bwd", "fm_maxpool2x2_nhwc", "fm_lpips_distance", "fm_lpips_tap_bwd", "fm_feat_distance", "fm_quick_gelu_bwd", "fm_quick_gelu_bwd_f32", "fm_clip_embed_ln_bwd", "fm_tap_add", "fm_clip_embed_ln", "fm_attn_decode", "fm_vit_patch_rows", "fm_vit_emb_rows", "fm_vit_colsum", "fm_lora_apply", "fm_lora_grad", "fm_vq_assign_wide", "fm_memcodes_assign", "fm_convnext_block", "fm_split3_bf16", "fm_unet_im2col", "fm_groupnorm_nhwc", "fm_add_bf16", "fm_silu_f32_to_bf16", "fm_timestep_embedding", "fm_unet_attention", "fm_diffusion_x0", "fm_quantile_abs",
            "fm_diffusion_step", "fm_unpack_image_u8", "fm_unpack_ids_u16", "fm_unpack_mask_bits", "fm_decoder_attention_from_target", "fm_guidance_combine", "fm_image_mask", "fm_token_budgets", "fm_span_mask", "fm_vq_code_stats", "fm_vq_ema_update", "fm_vq_code_bias", "fm_vq_assign_bias", "fm_vq_code_stats_raw", "fm_vq_ema_update_euclid", "fm_vq_unpatchify", "fm_vq_latent_grad", "fm_tanh_bwd_f32", "fm_embed_rows_f32", "fm_vq_patchify_ex", "fm_vq_cls_emb_bwd", "fm_vq_latent_grad_normalized", "fm_abi_version", "fm_last_error", "fm_gemm_nt", "fm_set_gemm_nt_config", "fm_get_gemm_nt_config", "fm_set_reserved_cus", "fm_get_reserved_cus", "fm_bf16_to_f32_scaled", "fm_add_bf16_f32", "fm_scale_rows_bf16", "fm_gemm_tn", "fm_gemm_tn_multi", "fm_set_gemm_tn_config", "fm_get_gemm_tn_config", "fm_set_tn_transpose_read",
            "fm_get_tn_transpose_read", "fm_layernorm_fwd", "fm_layernorm_fwd_res", "fm_layernorm_bwd", "fm_layernorm_bwd_h", "fm_headnorm_fwd", "fm_headnorm_bwd", "fm_attn_fwd", "fm_attn_bwd",
            "fm_set_attn_transpose_read", "fm_get_attn_transpose_read", "fm_select_embed", "fm_embed_bwd",

@@ -756,3 +756,73 @@ def vit_colsum(dy, db, ws, R=None):
     with _prof("colsum", 0.0, 4.0 * R * N):
         L.check(L.vit_colsum(_p(dy), _ld(dy), _p(db), R, N, _p(ws), ws.numel() * 8, _stream()))
     return db
+
+
+# ---------------------------------------------------------------------------------------------
+# tokenizer training objective (csrc/train_objective.hip)
+# ---------------------------------------------------------------------------------------------
+def reconst_loss(x, target, mode, grad=None):
+    """-> loss (1,) f32 of fm_reconst_loss on x (B, C, H, W) f32 contiguous; ``grad`` (x's shape or None) receives d loss / d x."""
+    B, C_ = x.shape[0], x.shape[1]
+    HW = x.numel() // (B * C_)
+    assert x.dtype == torch.float32 and x.is_contiguous() and target.is_contiguous() and (grad is None or (grad.dtype == torch.float32 and grad.is_contiguous()))
+    assert target.dtype == (torch.int64 if mode == L.LOSS_CE_INDEX else torch.float32)
+    n = L.reconst_loss_scratch(mode, B, C_, HW)
+    L.check(min(n, 0))
+    scratch = torch.empty(n, dtype=torch.float32, device=x.device)
+    loss = torch.empty(1, dtype=torch.float32, device=x.device)
+    with _prof("reconst_loss", 0.0, 4.0 * x.numel() * (2.0 + (grad is not None))):
+        L.check(L.reconst_loss(_p(x), _p(target), mode, B, C_, HW, _p(grad), _p(scratch), _p(loss), _stream()))
+    return loss
+
+
+def scale_f32(x, scale):
+    """x *= scale[0] in place (scale: a one-element f32 device tensor; exactly 1 leaves x alone) - fm_scale_f32."""
+    assert x.dtype == scale.dtype == torch.float32 and x.is_contiguous() and scale.numel() == 1
+    L.check(L.scale_f32(_p(x), _p(scale), x.numel(), _stream()))
+    return x
+
+
+def mask_out_samples(clean, valid_u8, mask_value, out):
+    """clean (B, C, H, W) f32 overwritten in place where valid_u8 (B, 1, H, W) is 0; out (B, C + 1, H, W) = [clean | valid * 2 - 1]."""
+    B, C_ = clean.shape[0], clean.shape[1]
+    HW = clean.numel() // (B * C_)
+    assert clean.dtype == out.dtype == torch.float32 and clean.is_contiguous() and out.is_contiguous() and out.numel() == B * (C_ + 1) * HW
+    assert valid_u8.dtype == torch.uint8 and valid_u8.is_contiguous() and valid_u8.numel() == B * HW
+    L.check(L.mask_out_samples(_p(clean), _p(valid_u8), float(mask_value), _p(out), B, C_, HW, _stream()))
+    return out
+
+
+def ema_jobs_table(pairs, device):
+    """pairs: [(ema, model)] f32 contiguous device tensors of equal sizes -> (device byte tensor of fm_ema_job, total chunks)."""
+    arr = (L.EmaJob * len(pairs))()
+    chunks = 0
+    for i, (e, m) in enumerate(pairs):
+        assert e.dtype == m.dtype == torch.float32 and e.is_contiguous() and m.is_contiguous() and e.numel() == m.numel() > 0 and e.device == m.device == device
+        arr[i].ema, arr[i].model, arr[i].n, arr[i].first_chunk = e.data_ptr(), m.data_ptr(), e.numel(), chunks
+        chunks += (e.numel() + L.EMA_CHUNK - 1) // L.EMA_CHUNK
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device), chunks
+
+
+def ema_update(table, n_jobs, chunks, decay):
+    """ema = ema * float(decay) + float(1 - decay) * model over the job list, one launch (1 - decay in double first, as Python forms it)."""
+    with _prof("ema_update", 0.0, 12.0 * chunks * L.EMA_CHUNK):
+        L.check(L.ema_update(_p(table), n_jobs, chunks, float(decay), float(1.0 - decay), _stream()))
+
+
+def diffusion_pair(clean, noise, timesteps, sqrt_alpha, sqrt_sigma, noisy, velocity=None):
+    B = clean.shape[0]
+    assert clean.dtype == noise.dtype == noisy.dtype == torch.float32 and clean.is_contiguous() and noise.is_contiguous() and noisy.is_contiguous()
+    assert timesteps.dtype == torch.int64 and timesteps.is_contiguous() and timesteps.numel() == B and sqrt_alpha.numel() == sqrt_sigma.numel()
+    assert velocity is None or (velocity.dtype == torch.float32 and velocity.is_contiguous())
+    L.check(L.diffusion_pair(_p(clean), _p(noise), _p(timesteps), _p(sqrt_alpha), _p(sqrt_sigma), sqrt_alpha.numel(), _p(noisy), _p(velocity), B,
+                             clean.numel() // B, _stream()))
+    return noisy, velocity
+
+
+def token_usage(tokens, n_windows, window, K, counts, bad):
+    """counts[w] (int32) = distinct tokens of window w; bad[0] (int32) = tokens outside [0, K)."""
+    assert tokens.dtype in (torch.int16, torch.int32, torch.int64) and tokens.is_contiguous() and tokens.numel() >= n_windows * window
+    assert counts.dtype == bad.dtype == torch.int32 and counts.numel() >= n_windows
+    L.check(L.token_usage(_p(tokens), tokens.element_size(), n_windows, window, K, _p(counts), _p(bad), _stream()))
+    return counts

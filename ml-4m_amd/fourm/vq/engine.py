@@ -45,6 +45,10 @@ class _VitEngine(FourMEngine):
     def device(self):
         return self.model.blocks[0].norm1.weight.device
 
+    def __deepcopy__(self, memo):
+        """A deep copy of the module (a weight EMA) does not share or clone scratch and cached weight images: it builds its own engine."""
+        return None
+
     def prepare(self):
         if self.ws is None or self.ws.device != self.device:
             self.ws = Workspace(self.device, per_stream=True)          # (sub-batches may be in flight on several streams: tokenize_sub_batches)
@@ -417,6 +421,9 @@ class _MlpEngine:
         self.device = device
         self.ws = Workspace(device, per_stream=True)
         self._cache = {}
+
+    def __deepcopy__(self, memo):
+        return None          # (as _VitEngine: the copied module builds its own)
 
 
 def _mlp_engine(mod, probe) -> _MlpEngine:
