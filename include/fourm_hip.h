@@ -887,6 +887,45 @@ int fm_diffusion_pair(const void* clean, const void* noise, const void* timestep
                       void* velocity, int B, int64_t per_sample, void* stream);
 int fm_token_usage(const void* tokens, int elem_size, int64_t n_windows, int64_t window, int K, void* counts, void* bad, void* stream);
 
+/* Tokenizer validation metrics (csrc/metrics.hip): the image metrics of upstream's eval_metrics (run_training_vqvae.py:1427-1632) - MSE, MAE,
+ * PSNR, MS-SSIM, IoU - and the token histogram.  Images are f32 (B, C, H, W) contiguous; only the first C_use channels of each sample are read,
+ * in place (prediction and target may have different channel counts).  transform is applied in the loads:
+ *     FM_METRIC_RAW: the values as they are;  FM_METRIC_DENORM: (v + 1) * 0.5 on both images, one fp32 add and an exact halving (upstream's
+ *     denormalize, TF.normalize with mean -1 and std 2);  FM_METRIC_SIGMOID_PRED: 1 / (1 + exp(-v)) on the prediction, the target raw.
+ * Per-element arithmetic is fp32, compiled without fused multiply-adds; every sum over elements, window positions and tiles is carried in double
+ * and added in a fixed order (per thread, shuffle tree, wavefronts, per-workgroup partials in caller-owned scratch, a second launch over the
+ * partials in index order).  No floating-point atomics: two calls on the same inputs give the same bits.  Integer atomics only where the order
+ * cannot matter (the IoU counts, the histogram).  No input value is used as an index without a range check.
+ *
+ * fm_metric_sums: with p, t the converted prediction and target and d = p - t rounded once,  sums[0] += sum d * d,  sums[1] += sum |d|  (f64
+ *   accumulators in device memory, each term formed in fp32),  counts[3] += B C_use HW  (counts: int64 (5) in device memory).  With iou != 0
+ *   also counts[0] += tp, counts[1] += fp, counts[2] += fn, counts[4] += the number of targets that are neither 0 nor 1, where the prediction
+ *   is positive when min(max(p, 0), 1) > threshold and the target when t == 1.  scratch: fm_metric_sums_scratch doubles (that function returns
+ *   the count, or -1).  Workgroup w takes elements [w, w + 1) FM_METRIC_CHUNK of the B C_use HW in (b, c, hw) order, whatever Cp and Ct are.
+ * fm_ssim_scale: SSIM of one scale with a separable window of ksize taps (f32 (ksize) in device memory; ksize odd, <= FM_SSIM_MAX_KERNEL) over
+ *   the valid positions only, (H - ksize + 1) (W - ksize + 1) per channel:  mu_x = sum g_i g_j x,  var_x = sum g_i g_j x^2 - mu_x^2,  cov = sum
+ *   g_i g_j x y - mu_x mu_y,  cs = (2 cov + c2) / (var_x + var_y + c2),  ssim = (2 mu_x mu_y + c1) / (mu_x^2 + mu_y^2 + c1) * cs.  ssim[b] and
+ *   cs[b] (f64 (B) in device memory) = the means over channels and positions of image b.  One workgroup per (plane, FM_SSIM_TILE^2 positions):
+ *   the haloed tile of both images in LDS, the five moments filtered along the rows, then the columns.  scratch: fm_ssim_scale_scratch doubles.
+ * fm_avgpool2x2_pair: xo, yo f32 (B, C_use, H / 2, W / 2) = the 2 x 2 mean with stride 2 of the converted first C_use channels of x and y,
+ *   ((a + b) + (c + d)) * 0.25; an odd last row or column is dropped (F.avg_pool2d).  The next scale reads xo, yo with FM_METRIC_RAW.
+ * fm_token_histogram: hist[v] += the number of tokens equal to v (hist: int64 (K) in device memory, zeroed by the caller; tokens int16 / int32 /
+ *   int64 by elem_size 2 / 4 / 8); bad[0] (int32) = the number of tokens outside [0, K), which are not counted.
+ * Refused (-1) before anything is written: null or misaligned pointers, non-positive sizes, C_use above a channel count, an unknown transform,
+ *   a window that is even, longer than FM_SSIM_MAX_KERNEL or longer than the image. */
+enum { FM_METRIC_RAW = 0, FM_METRIC_DENORM = 1, FM_METRIC_SIGMOID_PRED = 2 };
+#define FM_METRIC_CHUNK 4096
+#define FM_SSIM_TILE 32
+#define FM_SSIM_MAX_KERNEL 11
+int fm_metric_sums_scratch(int B, int C_use, int64_t HW);
+int fm_metric_sums(const void* pred, const void* target, int B, int Cp, int Ct, int C_use, int64_t HW, int transform, int iou, float threshold,
+                   void* scratch, void* sums, void* counts, void* stream);
+int fm_ssim_scale_scratch(int B, int C_use, int H, int W, int ksize);
+int fm_ssim_scale(const void* x, const void* y, int B, int Cx, int Cy, int C_use, int H, int W, int transform, const void* window, int ksize, float c1,
+                  float c2, void* scratch, void* ssim, void* cs, void* stream);
+int fm_avgpool2x2_pair(const void* x, const void* y, int B, int Cx, int Cy, int C_use, int H, int W, int transform, void* xo, void* yo, void* stream);
+int fm_token_histogram(const void* tokens, int elem_size, int64_t n, int K, void* hist, void* bad, void* stream);
+
 /* ---- lab (not part of the drop-in surface) ------------------------------------------------------------------------------------------
  * Experiment knobs of the GEMM kernels, used by tools/gemm_lab.cpp, the Python tools and the FOURM_NT3_LAB environment switch only: key 0 / 1
  * staggered workgroup start (groups, step), 2 gemm_nt3 mode override, 3 gemm_nt3 ablation flags (gemm_args.h NTArgs::lab), others reserved.

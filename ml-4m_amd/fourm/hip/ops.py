@@ -826,3 +826,55 @@ def token_usage(tokens, n_windows, window, K, counts, bad):
     assert counts.dtype == bad.dtype == torch.int32 and counts.numel() >= n_windows
     L.check(L.token_usage(_p(tokens), tokens.element_size(), n_windows, window, K, _p(counts), _p(bad), _stream()))
     return counts
+
+
+# ---------------------------------------------------------------------------------------------
+# tokenizer validation metrics (csrc/metrics.hip)
+# ---------------------------------------------------------------------------------------------
+def _image_pair(x, y, c_use):
+    assert x.dtype == y.dtype == torch.float32 and x.dim() == y.dim() == 4 and x.is_contiguous() and y.is_contiguous()
+    assert x.shape[0] == y.shape[0] and x.shape[2:] == y.shape[2:] and 0 < c_use <= min(x.shape[1], y.shape[1])
+    return x.shape[0], x.shape[1], y.shape[1], x.shape[2], x.shape[3]
+
+
+def metric_sums(pred, target, c_use, transform, sums, counts, iou=False, threshold=0.5):
+    """sums (2,) f64 += [sum d^2, sum |d|] and counts (5,) int64 += [tp, fp, fn, n, bad targets] (tp, fp, fn, bad only with ``iou``) over the
+    first ``c_use`` channels of pred / target (B, C, H, W) f32, converted by ``transform`` in the loads - fm_metric_sums."""
+    B, Cp, Ct, H, W = _image_pair(pred, target, c_use)
+    assert sums.dtype == torch.float64 and sums.numel() == 2 and counts.dtype == torch.int64 and counts.numel() == 5 and sums.is_contiguous() and counts.is_contiguous()
+    n = L.metric_sums_scratch(B, c_use, H * W)
+    L.check(min(n, 0))
+    scratch = torch.empty(n, dtype=torch.float64, device=pred.device)
+    with _prof("metric_sums", 0.0, 8.0 * B * c_use * H * W):
+        L.check(L.metric_sums(_p(pred), _p(target), B, Cp, Ct, c_use, H * W, transform, int(bool(iou)), float(threshold), _p(scratch), _p(sums), _p(counts), _stream()))
+
+
+def ssim_scale(x, y, c_use, transform, window, c1, c2, ssim, cs):
+    """ssim (B,), cs (B,) f64 = the per-image means of SSIM and of its contrast-structure term at one scale, window (k,) f32 taps - fm_ssim_scale."""
+    B, Cx, Cy, H, W = _image_pair(x, y, c_use)
+    assert window.dtype == torch.float32 and window.dim() == 1 and window.is_contiguous()
+    assert ssim.dtype == cs.dtype == torch.float64 and ssim.numel() == cs.numel() == B and ssim.is_contiguous() and cs.is_contiguous()
+    n = L.ssim_scale_scratch(B, c_use, H, W, window.numel())
+    L.check(min(n, 0))
+    scratch = torch.empty(n, dtype=torch.float64, device=x.device)
+    with _prof("ssim_scale", 0.0, 8.0 * B * c_use * H * W):
+        L.check(L.ssim_scale(_p(x), _p(y), B, Cx, Cy, c_use, H, W, transform, _p(window), window.numel(), float(c1), float(c2), _p(scratch), _p(ssim), _p(cs), _stream()))
+
+
+def avgpool2x2_pair(x, y, c_use, transform, xo=None, yo=None):
+    """-> (xo, yo) (B, c_use, H // 2, W // 2) f32: the 2 x 2 means of the converted first ``c_use`` channels of both images - fm_avgpool2x2_pair."""
+    B, Cx, Cy, H, W = _image_pair(x, y, c_use)
+    if xo is None:
+        xo = torch.empty(B, c_use, H // 2, W // 2, dtype=torch.float32, device=x.device)
+        yo = torch.empty_like(xo)
+    assert xo.dtype == yo.dtype == torch.float32 and xo.is_contiguous() and yo.is_contiguous() and xo.numel() == yo.numel() == B * c_use * (H // 2) * (W // 2)
+    L.check(L.avgpool2x2_pair(_p(x), _p(y), B, Cx, Cy, c_use, H, W, transform, _p(xo), _p(yo), _stream()))
+    return xo, yo
+
+
+def token_histogram(tokens, K, hist, bad):
+    """hist (K,) int64 += occurrences of every token value; bad[0] (int32) = tokens outside [0, K) - fm_token_histogram."""
+    assert tokens.dtype in (torch.int16, torch.int32, torch.int64) and tokens.is_contiguous()
+    assert hist.dtype == torch.int64 and hist.numel() == K and hist.is_contiguous() and bad.dtype == torch.int32
+    L.check(L.token_histogram(_p(tokens), tokens.element_size(), tokens.numel(), K, _p(hist), _p(bad), _stream()))
+    return hist
