@@ -926,6 +926,49 @@ int fm_ssim_scale(const void* x, const void* y, int B, int Cx, int Cy, int C_use
 int fm_avgpool2x2_pair(const void* x, const void* y, int B, int Cx, int Cy, int C_use, int H, int W, int transform, void* xo, void* yo, void* stream);
 int fm_token_histogram(const void* tokens, int elem_size, int64_t n, int K, void* hist, void* bad, void* stream);
 
+/* Image resize (csrc/resize.hip): F.interpolate with a given size and align_corners = False, as upstream's tokenizer trainer uses it
+ * (run_training_vqvae.py prepare_inputs :881-958; the Resize of the CLIP loss's percept_transform) - bilinear, antialiased bilinear and
+ * nearest - with the adjoint of the two bilinear modes.  fp32 planes (planes = B C, H, W) contiguous.  Both bilinear modes are separable:
+ * one axis is a table (start[o], count[o], weights[o][taps]) per output index o, output o = sum_k weights[o][k] * input[start[o] + k].
+ *
+ * fm_resize_axis_table: HOST function, no GPU call.  Fills the table of one axis into caller-owned HOST arrays (any of them may be NULL):
+ *   start, count int32 (n_out); weights f32 (n_out, taps) = the weights computed in double and rounded once, rows padded with zeros;
+ *   weights_f64 the same before rounding; t_start, t_count int32 (n_in) = the transposed description: input i is read by exactly the outputs
+ *   [t_start[i], t_start[i] + t_count[i]) (contiguous because start and start + count do not decrease; t_count[i] = 0 where no output reads
+ *   i, and t_start does not decrease either).  Returns taps = max count (call once with NULLs to size the weights), or -1.  With scale =
+ *   n_in / n_out in double:
+ *     FM_RESIZE_BILINEAR:    s = max(scale (o + 0.5) - 0.5, 0), i0 = min(floor(s), n_in - 1), i1 = min(i0 + 1, n_in - 1), weights 1 - (s - i0), s - i0;
+ *     FM_RESIZE_BILINEAR_AA: support = max(scale, 1), inv = min(1 / scale, 1), c = scale (o + 0.5), xmin = max(int(c - support + 0.5), 0),
+ *                            xsize = min(int(c + support + 0.5), n_in) - xmin, w_j = max(0, 1 - |(j + xmin - c + 0.5) inv|) / their sum;
+ *     FM_RESIZE_NEAREST:     i = min(floorf(fp32(o) * (fp32(n_in) / fp32(n_out))), n_in - 1), one tap of weight 1.
+ *   Taps of weight zero at either end of a window are dropped (i0 = i1 becomes one tap of weight 1), so every stored tap inside count is
+ *   non-zero.  Windows wider than FM_RESIZE_MAX_TAPS and sizes above 2^24 are refused.
+ * fm_resize_bilinear_fwd: y[p] = a_c R(x[p]) + b_c, c = p mod C, one fused multiply-add on the filtered value; scale (a) and shift (b) are
+ *   f32 (C) in device memory or NULL (both or neither; NULL = identity).  Tables in DEVICE memory, as fm_resize_axis_table made them for
+ *   (H_in, H_out) and (W_in, W_out).  One launch: a workgroup owns a tile of outputs, stages the tile's input window and table rows in LDS,
+ *   filters along the rows into LDS, then along the columns.  The tile (at most 32 x 32) is the largest whose window fits 64 KiB of LDS.
+ * fm_resize_bilinear_bwd: dx[p] = a_c R^T(dy[p]) as a gather over the transposed tables: a workgroup owns a tile of INPUT pixels, stages the
+ *   window of dy that reads them (tiles of at most 64 x 64), and every input pixel sums its covering outputs in index order.  One launch, no
+ *   atomics.
+ * fm_resize_nearest: y[p][oh][ow] = x[p][index_h[oh]][index_w[ow]] for elements of elem_size 4 (f32) or 8 (int64 class maps); index_h, index_w
+ *   int32 (H_out), (W_out) in device memory (the start array of FM_RESIZE_NEAREST), clamped into the image.
+ * Two calls on the same inputs give the same bits.  Refused (-1) before any launch: null or misaligned pointers, non-positive sizes, taps
+ * outside [1, FM_RESIZE_MAX_TAPS], a geometry whose smallest tile does not fit the LDS.  The kernels never index by a table entry they have not
+ * range-checked: a tile whose table rows are inconsistent with the sizes is filled with NaN. */
+enum { FM_RESIZE_BILINEAR = 0, FM_RESIZE_BILINEAR_AA = 1, FM_RESIZE_NEAREST = 2 };
+#define FM_RESIZE_MAX_TAPS 64
+int fm_resize_axis_table(int n_in, int n_out, int mode, int32_t* start, int32_t* count, float* weights, double* weights_f64, int32_t* t_start,
+                         int32_t* t_count);
+int fm_resize_bilinear_fwd(const void* x, void* y, int planes, int H_in, int W_in, int H_out, int W_out, const void* start_h, const void* count_h,
+                           const void* weights_h, int taps_h, const void* start_w, const void* count_w, const void* weights_w, int taps_w,
+                           const void* scale, const void* shift, int C, void* stream);
+int fm_resize_bilinear_bwd(const void* dy, void* dx, int planes, int H_in, int W_in, int H_out, int W_out, const void* start_h, const void* count_h,
+                           const void* weights_h, int taps_h, const void* t_start_h, const void* t_count_h, const void* start_w,
+                           const void* count_w, const void* weights_w, int taps_w, const void* t_start_w, const void* t_count_w,
+                           const void* scale, int C, void* stream);
+int fm_resize_nearest(const void* x, void* y, int elem_size, int planes, int H_in, int W_in, int H_out, int W_out, const void* index_h,
+                      const void* index_w, void* stream);
+
 /* ---- lab (not part of the drop-in surface) ------------------------------------------------------------------------------------------
  * Experiment knobs of the GEMM kernels, used by tools/gemm_lab.cpp, the Python tools and the FOURM_NT3_LAB environment switch only: key 0 / 1
  * staggered workgroup start (groups, step), 2 gemm_nt3 mode override, 3 gemm_nt3 ablation flags (gemm_args.h NTArgs::lab), others reserved.

@@ -878,3 +878,74 @@ def token_histogram(tokens, K, hist, bad):
     assert hist.dtype == torch.int64 and hist.numel() == K and hist.is_contiguous() and bad.dtype == torch.int32
     L.check(L.token_histogram(_p(tokens), tokens.element_size(), tokens.numel(), K, _p(hist), _p(bad), _stream()))
     return hist
+
+
+# ---------------------------------------------------------------------------------------------
+# image resize, forward and adjoint (csrc/resize.hip)
+# ---------------------------------------------------------------------------------------------
+def resize_axis_table(n_in, n_out, mode):
+    """fm_resize_axis_table on the host -> dict of CPU tensors: start, count int32 (n_out), weights f32 and weights_f64 (n_out, taps), t_start,
+    t_count int32 (n_in), and the ints taps and t_taps (the largest count / t_count).  No GPU call."""
+    taps = L.resize_axis_table(n_in, n_out, mode, None, None, None, None, None, None)
+    L.check(min(taps, 0))
+    start, count = torch.empty(n_out, dtype=torch.int32), torch.empty(n_out, dtype=torch.int32)
+    w32, w64 = torch.empty(n_out, taps, dtype=torch.float32), torch.empty(n_out, taps, dtype=torch.float64)
+    ts, tc = torch.empty(n_in, dtype=torch.int32), torch.empty(n_in, dtype=torch.int32)
+
+    def ptr(t, ct):
+        return C.cast(t.data_ptr(), C.POINTER(ct))
+    got = L.resize_axis_table(n_in, n_out, mode, ptr(start, C.c_int32), ptr(count, C.c_int32), ptr(w32, C.c_float), ptr(w64, C.c_double), ptr(ts, C.c_int32),
+                              ptr(tc, C.c_int32))
+    L.check(min(got, 0))
+    assert got == taps
+    return dict(start=start, count=count, weights=w32, weights_f64=w64, t_start=ts, t_count=tc, taps=taps, t_taps=int(tc.max()))
+
+
+def _resize_axis_ok(t, n_in, n_out):
+    return (t["start"].dtype == t["count"].dtype == t["t_start"].dtype == t["t_count"].dtype == torch.int32 and t["weights"].dtype == torch.float32
+            and t["start"].numel() == t["count"].numel() == n_out and t["weights"].numel() == n_out * t["taps"] and t["t_start"].numel() == t["t_count"].numel() == n_in
+            and all(t[k].is_contiguous() for k in ("start", "count", "weights", "t_start", "t_count")))
+
+
+def _resize_affine(scale, shift, C_):
+    for v in (scale, shift):
+        assert v is None or (v.dtype == torch.float32 and v.is_contiguous() and v.numel() == C_)
+
+
+def resize_bilinear_fwd(x, y, th, tw, scale=None, shift=None):
+    """y (B, C, H_out, W_out) = scale[c] * R(x) + shift[c] for x (B, C, H_in, W_in) f32 - fm_resize_bilinear_fwd.  th, tw: the axis tables
+    on x's device (dicts as resize_axis_table returns them, for the rows and the columns)."""
+    B, C_, Hi, Wi = x.shape
+    Ho, Wo = y.shape[2], y.shape[3]
+    assert x.dtype == y.dtype == torch.float32 and x.is_contiguous() and y.is_contiguous() and y.shape[:2] == x.shape[:2]
+    assert _resize_axis_ok(th, Hi, Ho) and _resize_axis_ok(tw, Wi, Wo) and (scale is None) == (shift is None)
+    _resize_affine(scale, shift, C_)
+    with _prof("resize_bilinear_fwd", 0.0, 4.0 * (x.numel() + y.numel())):
+        L.check(L.resize_bilinear_fwd(_p(x), _p(y), B * C_, Hi, Wi, Ho, Wo, _p(th["start"]), _p(th["count"]), _p(th["weights"]), th["taps"],
+                                      _p(tw["start"]), _p(tw["count"]), _p(tw["weights"]), tw["taps"], _p(scale), _p(shift), C_, _stream()))
+    return y
+
+
+def resize_bilinear_bwd(dy, dx, th, tw, scale=None):
+    """dx (B, C, H_in, W_in) = scale[c] * R^T(dy) for dy (B, C, H_out, W_out) f32: the adjoint of resize_bilinear_fwd as a gather, no atomics -
+    fm_resize_bilinear_bwd."""
+    B, C_, Hi, Wi = dx.shape
+    Ho, Wo = dy.shape[2], dy.shape[3]
+    assert dx.dtype == dy.dtype == torch.float32 and dx.is_contiguous() and dy.is_contiguous() and dy.shape[:2] == dx.shape[:2]
+    assert _resize_axis_ok(th, Hi, Ho) and _resize_axis_ok(tw, Wi, Wo)
+    _resize_affine(scale, None, C_)
+    with _prof("resize_bilinear_bwd", 0.0, 4.0 * (dx.numel() + dy.numel())):
+        L.check(L.resize_bilinear_bwd(_p(dy), _p(dx), B * C_, Hi, Wi, Ho, Wo, _p(th["start"]), _p(th["count"]), _p(th["weights"]), th["taps"],
+                                      _p(th["t_start"]), _p(th["t_count"]), _p(tw["start"]), _p(tw["count"]), _p(tw["weights"]), tw["taps"],
+                                      _p(tw["t_start"]), _p(tw["t_count"]), _p(scale), C_, _stream()))
+    return dx
+
+
+def resize_nearest(x, y, index_h, index_w):
+    """y (..., H_out, W_out) = x (..., H_in, W_in) gathered at (index_h[oh], index_w[ow]) for f32 or int64 elements - fm_resize_nearest."""
+    assert x.dtype == y.dtype and x.dtype in (torch.float32, torch.int64) and x.is_contiguous() and y.is_contiguous() and x.dim() == y.dim() >= 3
+    assert x.shape[:-2] == y.shape[:-2] and index_h.dtype == index_w.dtype == torch.int32 and index_h.is_contiguous() and index_w.is_contiguous()
+    Hi, Wi, Ho, Wo = x.shape[-2], x.shape[-1], y.shape[-2], y.shape[-1]
+    assert index_h.numel() == Ho and index_w.numel() == Wo
+    L.check(L.resize_nearest(_p(x), _p(y), x.element_size(), x.numel() // (Hi * Wi), Hi, Wi, Ho, Wo, _p(index_h), _p(index_w), _stream()))
+    return y

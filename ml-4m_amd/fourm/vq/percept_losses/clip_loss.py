@@ -11,7 +11,8 @@ image, compared token by token.  The gradient flows through the tower back to th
     projection transposed; fm_vq_unpatchify.
 
 Not here: fetching or converting timm checkpoints (build the tower from an OpenAI CLIP state dict: ``fourm.utils.clip.model.build_visual``),
-DINOv2 or other feature networks, a trainable tower, resizing to the tower's input size (LPIPS: lpips_loss.py)."""
+DINOv2 or other feature networks, a trainable tower (LPIPS: lpips_loss.py).  Images of another size than the tower's are refused here;
+``fourm.vq.training.perceptual_loss`` resizes them in front of this module (fm_resize_bilinear_fwd / _bwd with this module's affine folded in)."""
 import torch
 from torch import nn
 

@@ -5,18 +5,28 @@ backward and the perceptual losses (``fourm.vq.percept_losses``), as a library a
     mask_out_samples         run_training_vqvae.py:857-878 (fm_mask_out_samples)
     ModelEma                 fourm/utils/timm/model_ema.py:39-81; ``update`` is one launch over a device job list (fm_ema_update)
     diffusion_training_pair  the noised input and the regression target of a DiVAE step, run_training_divae.py:966-986 (fm_diffusion_pair)
+    resize_images            F.interpolate at a given size, bilinear (optionally antialiased, optionally with a per-channel affine in the same
+                             launch) and nearest; differentiable (fourm.vq.resize: fm_resize_bilinear_fwd / _bwd, fm_resize_nearest)
+    prepare_inputs           run_training_vqvae.py:881-958 for the domains that need no feature network: the per-step resize and the masking
+    perceptual_loss          run_training_vqvae.py:1146-1148: the perceptual term at any resolution (the CLIP loss's antialiased Resize and its
+                             normalisation as one launch per tensor)
 
 ``fourm.vq.vq_utils.compute_codebook_usage`` (fm_token_usage) lives in upstream's module of that name.  Everything is fp32; the kernels are
-csrc/train_objective.hip.  Tensors on the CPU raise RuntimeError (there is no CPU path), except where a function says otherwise.
+csrc/train_objective.hip and csrc/resize.hip.  Tensors on the CPU raise RuntimeError (there is no CPU path), except where a function says
+otherwise.
 
-Not here: the trainer scripts themselves, their data loaders and the Inception metrics of evaluation."""
+Not here: the trainer scripts themselves, their data loaders, feature extractors (CLIP / DINOv2 / ImageBind targets computed on the fly) and the
+Inception metrics of evaluation."""
 from collections import OrderedDict
 from copy import deepcopy
-from typing import Optional, Tuple
+from typing import Dict, Optional, Tuple, Union
 
 import torch
 
+from fourm.vq.resize import resize_images
+
 LOSS_FNS = ("mse", "l1", "smooth_l1", "cross_entropy", "binary_cross_entropy", "cosine", "cosine_1d")
+FEAT_MODALITIES = ['CLIP-B16', 'CLIP-L14', 'DINOv2-B14', 'DINOv2-B14-global', 'DINOv2-G14', 'DINOv2-G14-global', 'ImageBind-H14', 'ImageBind-H14-global']
 
 
 def _on_gpu(what, *tensors):
@@ -106,6 +116,68 @@ def mask_out_samples(clean_inputs: torch.Tensor, mask_valid: Optional[torch.Tens
         if work is not clean_inputs:
             clean_inputs.copy_(work)
     return out
+
+
+# ---- per-step input preparation -----------------------------------------------------------------------------------------------------------------
+def prepare_inputs(x: Dict[str, torch.Tensor], domain: str, feature_extractor: Optional[torch.nn.Module], device: Union[torch.device, str],
+                   image_size: Optional[int] = None, mask_value: Optional[float] = None) -> torch.Tensor:
+    """Upstream's ``prepare_inputs`` for the domains that need no feature network: take the domain's entry of the batch dict to ``device``,
+    resize it to ``image_size`` (an int or (H, W); None: as it is) and mask out the invalid regions.
+
+    Image-like domains: bilinear, align_corners=False (resize_images).  ``semseg*``: nearest on the integer class map (B, H, W), dtype kept.
+    ``sam_mask*``: ``x[domain]['instance']`` (B, N, H, W) flattened to (B N, 1, H, W), the instances with ``x[domain]['valid']`` selected; no
+    resize.  ``human_poses``: no resize, two trailing axes added.  Then ``mask_out_samples(images, x.get('mask_valid'), mask_value)``.
+    A domain of ``FEAT_MODALITIES`` reads ``x['rgb']``; with a ``feature_extractor`` it raises NotImplementedError: feature networks are out
+    of scope here (extract the features before, or pass None to get the resized RGB)."""
+    if domain in FEAT_MODALITIES:
+        if feature_extractor is not None:
+            raise NotImplementedError(f"prepare_inputs: domain {domain!r} with a feature_extractor - feature networks (CLIP / DINOv2 / ImageBind targets "
+                                      "computed on the fly) are out of scope of this package's trainer pieces")
+        images = x['rgb'].to(device, non_blocking=True)
+    elif 'sam_mask' in domain:
+        images, valid = x[domain]['instance'], x[domain]['valid']
+        images = images.flatten(end_dim=1).unsqueeze(1)
+        images = images[valid.flatten().to(images.device)].to(device, non_blocking=True)
+    else:
+        images = x[domain].to(device, non_blocking=True)
+    if image_size is not None and 'human_poses' not in domain and 'sam_mask' not in domain:
+        if 'semseg' in domain:
+            if images.is_floating_point():
+                images = resize_images(images.float().unsqueeze(1), image_size, mode='nearest').to(images.dtype).squeeze(1)
+            else:
+                images = resize_images(images.to(torch.int64), image_size, mode='nearest').to(images.dtype)
+        else:
+            images = resize_images(images, image_size, mode='bilinear')
+    if 'human_poses' in domain:
+        images = images.unsqueeze(2).unsqueeze(2)
+    return mask_out_samples(images, x.get('mask_valid', None), mask_value=mask_value)
+
+
+# ---- perceptual term ----------------------------------------------------------------------------------------------------------------------------
+def perceptual_loss(loss_fn, model_output: torch.Tensor, images: torch.Tensor) -> torch.Tensor:
+    """``loss_fn(transform(model_output), transform(images)).mean()`` with the loss's own ``percept_transform`` - the perceptual term of
+    upstream's training and validation loops - at any image resolution.
+
+    ClipPerceptualLoss: at the tower's resolution the transform is its ``percept_transform``.  At any other, upstream's Normalize, Normalize,
+    Resize(res, bilinear, antialias) becomes ONE launch per tensor: the antialiased resize with the loss's per-channel affine folded in (the
+    weights of a window sum to 1, so R(a x + b) = a R(x) + b: upstream's order up to rounding), and the gradient comes back through the
+    adjoint kernel.  LpipsPerceptualLoss: the identity, as upstream.  A wrapped loss (``.module``) is unwrapped for the transform only."""
+    from fourm.vq.percept_losses import ClipPerceptualLoss, LpipsPerceptualLoss
+    inner = loss_fn.module if hasattr(loss_fn, "module") else loss_fn
+    if isinstance(inner, ClipPerceptualLoss):
+        _on_gpu("perceptual_loss", model_output, images)
+        res = inner.visual.input_resolution
+        if model_output.dim() != 4 or model_output.shape != images.shape:
+            raise ValueError(f"model_output {tuple(model_output.shape)} and images {tuple(images.shape)}: two (B, 3, H, W) batches of one shape expected")
+        if tuple(model_output.shape[-2:]) == (res, res):
+            transform = inner.percept_transform
+        else:
+            def transform(t):
+                return resize_images(t.float(), res, mode="bilinear", antialias=True, scale=inner._scale, shift=inner._shift)
+        return loss_fn(transform(model_output), transform(images), preprocess_inputs=False).mean()
+    if isinstance(inner, LpipsPerceptualLoss):
+        return loss_fn(model_output, images).mean()
+    raise TypeError(f"perceptual_loss: a ClipPerceptualLoss or LpipsPerceptualLoss expected, got {type(inner).__name__}")
 
 
 # ---- weight EMA -----------------------------------------------------------------------------------------------------------------------------
