@@ -969,6 +969,64 @@ int fm_resize_bilinear_bwd(const void* dy, void* dx, int planes, int H_in, int W
 int fm_resize_nearest(const void* x, void* y, int elem_size, int planes, int H_in, int W_in, int H_out, int W_out, const void* index_h,
                       const void* index_w, void* stream);
 
+/* Pillow-exact crops (csrc/pil_resize.hip): the data stage of upstream's save_vq_tokens.py - PIL.Image.crop + Image.resize + horizontal flip
+ * of 8-bit images - byte for byte.  Source: uint8 (H, W, C), 1 <= C <= 4.  One crop: (top, left, h, w, flip) inside the image, target S x S.
+ * Result: np.asarray(img.crop((left, top, left + w, top + h)).resize((S, S), resample)), then the flip.
+ *
+ * Filter modes (FM_PIL_BILINEAR, support 1; FM_PIL_BICUBIC, support 2), one axis of length n (the crop's) to S, everything in double, in this
+ * order, without fused multiply-add:  scale = n / S, fs = max(scale, 1), support = filter_support * fs;  per output o: center = (o + 0.5) *
+ * scale, xmin = max(int(center - support + 0.5), 0), xmax = min(int(center + support + 0.5), n), taps x = 0 .. xmax - xmin - 1 with k[x] =
+ * filter((x + xmin - center + 0.5) * (1 / fs)), ww = their sum in tap order, k[x] /= ww where ww != 0, and the integer coefficient
+ * int(0.5 + k * 2^22) for k >= 0, int(-0.5 + k * 2^22) for k < 0 (C truncation).  bilinear(x) = 1 - |x| below 1;  bicubic(x), a = -0.5:
+ * ((a + 2)|x| - (a + 3)) * |x| * |x| + 1 below 1, (((|x| - 5)|x| + 8)|x| - 4) * a below 2, else 0.  A pass computes acc = 2^21 + sum pixel *
+ * coef in int32 and out = clamp(acc >> 22, 0, 255) (arithmetic shift).  The horizontal pass runs first, over the crop's rows, into a uint8
+ * intermediate (h, S, C) - that rounding is part of the contract - then the vertical pass.  A pass whose size does not change is the
+ * identity (its table is the single coefficient 2^22).
+ * FM_PIL_NEAREST: Pillow's affine scaler: a = n / S in double, xo = a * 0.5, per output idx = int(xo), then xo += a (repeated addition; the
+ * closed form int((o + 0.5) * a) is NOT the same table).
+ * Flip, after the resize: columns reversed; channels in invert_mask (bit c) become 255 - v (channel 0 of surface normals).
+ * Four-channel images are four plain 8-bit planes (CMYK, RGBX); the premultiplication Pillow wraps around RGBA / LA resizes is not applied.
+ * Both entry points were ADDED without raising FM_ABI_VERSION (it stays 11: nothing that existed changed its meaning); a caller that needs
+ * them checks for the symbols, not for the version.
+ *
+ * fm_pil_axis_table: HOST function, no GPU call.  Fills start, count int32 (n_out) and coef int32 (n_out, taps), rows padded with zeros, for
+ *   one axis and filter (NULLs allowed); returns taps = the largest count (call once with NULLs to size coef), or -1.  FM_PIL_NEAREST and
+ *   n_in = n_out give one tap per output: start = the index, count = 1, coef = 2^22.  Windows above FM_PIL_MAX_TAPS are refused.
+ * fm_pil_crop_resize: n_jobs crops in two launches (rows, then columns).  jobs_dev: the DEVICE copy of jobs_host (8-byte aligned); the host
+ *   copy is validated completely before the first launch.  src: packed uint8 images (src_bytes);  tables: packed int32 axis tables
+ *   (table_words), the table of one axis laid out start (S) | count (S) | coef (S, taps);  scratch: caller-owned uint8 (scratch_bytes) for
+ *   the intermediates.  Outputs (any may be NULL, not all): out_u8 uint8 (n_slots, S, S, C);  out_f32 f32 (n_slots, C, S, S) = lut[c][v],
+ *   lut f32 (C, 256) in device memory;  out_i64 int64 (n_slots, S, S), C = 1 only.  Job i owns workgroups [blk_rows, blk_rows + ceil(h S /
+ *   256)) of the first launch and [blk_cols, blk_cols + ceil(S S / 256)) of the second, both prefix sums over the jobs in order.
+ * Refused (-1) before any launch: a box that leaves its image, an image, table, intermediate or slot outside its buffer, first workgroups
+ * that are not the prefix sums, a launch of 2^24 workgroups or more, C outside 1 .. 4, out_i64 with C != 1, out_f32 without lut.  The kernels use a table entry as an index only
+ * after checking it against the crop (a pixel whose table row is inconsistent is written as 0).  Two calls give the same bytes. */
+enum { FM_PIL_NEAREST = 0, FM_PIL_BILINEAR = 1, FM_PIL_BICUBIC = 2 };
+#define FM_PIL_MAX_TAPS 1024
+typedef struct fm_pil_crop_job {
+    int64_t src_off;  /* byte offset of the source image in src */
+    int64_t mid_off;  /* byte offset of this crop's (h, S, C) intermediate in scratch */
+    int64_t out_slot; /* index of the crop in the outputs */
+    int64_t blk_rows; /* first workgroup of the rows launch */
+    int64_t blk_cols; /* first workgroup of the columns launch */
+    int32_t H;        /* source size */
+    int32_t W;
+    int32_t top;      /* the box */
+    int32_t left;
+    int32_t h;
+    int32_t w;
+    int32_t flip;     /* 0 or 1 */
+    int32_t tab_w;    /* int32-word offset in tables of the table w -> S (rows launch) */
+    int32_t tab_h;    /* the same of h -> S (columns launch) */
+    int32_t taps_w;   /* row lengths of their coef arrays */
+    int32_t taps_h;
+    int32_t pad_;
+} fm_pil_crop_job;
+int fm_pil_axis_table(int n_in, int n_out, int filter, int32_t* start, int32_t* count, int32_t* coef);
+int fm_pil_crop_resize(const fm_pil_crop_job* jobs_host, const void* jobs_dev, int n_jobs, const void* src, int64_t src_bytes, const void* tables,
+                       int64_t table_words, void* scratch, int64_t scratch_bytes, int C, int S, int invert_mask, const void* lut, void* out_u8,
+                       void* out_f32, void* out_i64, int64_t n_slots, void* stream);
+
 /* ---- lab (not part of the drop-in surface) ------------------------------------------------------------------------------------------
  * Experiment knobs of the GEMM kernels, used by tools/gemm_lab.cpp, the Python tools and the FOURM_NT3_LAB environment switch only: key 0 / 1
  * staggered workgroup start (groups, step), 2 gemm_nt3 mode override, 3 gemm_nt3 ablation flags (gemm_args.h NTArgs::lab), others reserved.

@@ -14,7 +14,8 @@ is published only after its blocking host-to-device copies have returned, so a l
 because of those copies the first use of a size pair cannot happen inside a hipGraph capture (use the sizes once before capturing).  Entries are
 a few KiB; a trainer uses a handful of sizes.
 
-Not here: bicubic, scale factors, align_corners=True, crop / flip augmentation."""
+Not here: bicubic, scale factors, align_corners=True.  The crop / flip augmentation of dataset pre-tokenization on 8-bit images (Pillow's bytes,
+bicubic included) is ``fourm.data.crops``."""
 import threading
 
 import torch
