@@ -1027,7 +1027,55 @@ int fm_pil_crop_resize(const fm_pil_crop_job* jobs_host, const void* jobs_dev, i
                        int64_t table_words, void* scratch, int64_t scratch_bytes, int C, int S, int invert_mask, const void* lut, void* out_u8,
                        void* out_f32, void* out_i64, int64_t n_slots, void* stream);
 
-/* ---- lab (not part of the drop-in surface) ------------------------------------------------------------------------------------------
+/* Pillow-exact 16-bit depth crops (csrc/pil_resize16.hip): PIL.Image.crop + Image.resize + horizontal flip of mode "I;16" images (16-bit
+ * depth PNGs) - byte for byte - and upstream's DepthTransform.truncated_depth_standardization on the result.  Source: uint16 (H, W).
+ * Result of one crop (top, left, h, w, flip), target S x S: np.asarray(img.crop((left, top, left + w, top + h)).resize((S, S), resample)),
+ * then the flip.
+ *
+ * Pillow resamples "I;16" through ImagingResampleHorizontal/Vertical_16bpc, not the 8-bit integer path: the coefficients are the normalised
+ * DOUBLES of the section above - exactly what fm_pil_axis_table computes before it quantises to 2^22 (k = filter((x + xmin - center + 0.5) *
+ * ss), ww summed left to right, k / ww where ww != 0).  One output sample of a pass that resamples: ss = 0.0; for each tap in order ss +=
+ * (double)in[x] * k[x], the product and the sum rounded separately (NO fused multiply-add, on the device either); r = (int)(ss < 0 ? ss -
+ * 0.5 : ss + 0.5); low byte = clip8(r % 256) with C's remainder sign, high byte = clip8(r >> 8), clip8 the clamp to 0 .. 255.  The clamp is
+ * PER BYTE, not a clamp of r to 0 .. 65535: bicubic overshoot next to a saturated region gives a high byte of 255 and the low byte of r.
+ * The horizontal pass runs first, over the crop's rows, into a uint16 intermediate (h, S) - that rounding is part of the contract - then the
+ * vertical pass.  An axis whose crop length equals S is not resampled (Pillow skips that pass; its table is the single coefficient 1.0 and the
+ * sample is copied).  FM_PIL_NEAREST: both axes are index gathers, idx = int((o + 0.5) * a), a = n / S in double.  This is NOT the repeated-
+ * addition table of the section above: Pillow sends "I;16" (a "special" image type) through its generic affine transform, which evaluates
+ * the coordinate of every output pixel in closed form, and not through the 8-bit affine scaler; the two tables differ on about one axis in
+ * twenty (8 -> 7 is one).  The flip is applied last.  Modes "I", "F" and big-endian "I;16B" are outside this contract.
+ *
+ * Truncated standardisation of one crop of n = S S values v (0 .. 65535): lo = int(0.1 * n) and hi = int((1 - 0.1) * n) are computed by the
+ * CALLER in double (Python's) and passed in, m = hi - lo >= 2.  Over the elements of sorted rank lo .. hi - 1 the exact integers M1 = sum v
+ * and M2 = sum v^2;  mean = M1 / (m * 65535), one correctly rounded double division of two exactly representable integers;  var = (m M2 -
+ * M1^2) / (m (m - 1) 65535^2): numerator and denominator are exact wide integers, each converted to double with one correct rounding (above
+ * 64 bits: shifted to 64 bits with a sticky bit, converted, scaled back), then divided;  mean32 = (float)mean, var32 = (float)var;  x =
+ * (float)((double)v / 65535.0) - what torch.Tensor(np.array(img) / (2**16 - 1.0)) holds - and out = (x - mean32) / sqrtf(var32 + 1e-6f) in
+ * separately rounded fp32 operations.  The statistics are integer sums: they do not depend on the order of the reduction, two calls or two
+ * workgroup shapes give the same bits.  No sort: the rank boundaries are found by a two-level 256-bin histogram select in LDS (integer LDS
+ * atomics only, no floating-point atomics), one workgroup per crop;  the boundary values contribute only the share of their ties inside the
+ * rank range.  Upstream sums in fp32, so its own result differs from this by the rounding of its sums (INTEGRATION.md has the measured figure).
+ * The entry points were ADDED without raising FM_ABI_VERSION (it stays 11); a caller that needs them checks for the symbols.
+ *
+ * fm_pil_axis_table_f64: HOST function, no GPU call.  As fm_pil_axis_table with coef double (n_out, taps): the same start, count and taps
+ *   from the same computation, the coefficients before quantisation.  FM_PIL_NEAREST and n_in = n_out: one tap of coefficient 1.0;  the
+ *   start of FM_PIL_NEAREST is the closed-form index above (the one difference from fm_pil_axis_table's start and count).
+ * fm_pil_crop_resize16: n_jobs crops in two launches (rows, then columns) over the fm_pil_crop_job list of the section above, with src_off
+ *   and mid_off in bytes (both even) and tab_w / tab_h in int32 words (both even).  src: packed uint16 images (src_bytes);  tables (8-byte aligned, table_words int32 words): the
+ *   table of one axis laid out start int32 (S) | count int32 (S) | coef double (S, taps), S (2 + 2 taps) words;  scratch: caller-owned
+ *   (scratch_bytes) for the uint16 intermediates (h, S).  Outputs (either may be NULL, not both): out_i32 int32 (n_slots, S, S), the uint16
+ *   values;  out_f32 f32 (n_slots, 1, S, S) = (float)((double)v / 65535.0).  Workgroups as in fm_pil_crop_resize.  The host copy of every job
+ *   is validated before the first launch, with the refusals of fm_pil_crop_resize; a table entry is used as an index only after a check
+ *   against the crop (a sample whose table row is inconsistent is written as 0).  Two calls give the same bytes.
+ * fm_depth_standardize: values int32 (n_crops, n), each 0 .. 65535 (a value outside is read as its low 16 bits) -> out_f32 f32 (n_crops, n)
+ *   (may be NULL) and stats f32 (n_crops, 2) = (mean32, var32) (may be NULL, not both).  One workgroup per crop.  Refused (-1): n < 2,
+ *   n > 2^28, lo < 0, hi > n, hi - lo < 2. */
+int fm_pil_axis_table_f64(int n_in, int n_out, int filter, int32_t* start, int32_t* count, double* coef);
+int fm_pil_crop_resize16(const fm_pil_crop_job* jobs_host, const void* jobs_dev, int n_jobs, const void* src, int64_t src_bytes, const void* tables,
+                         int64_t table_words, void* scratch, int64_t scratch_bytes, int S, void* out_i32, void* out_f32, int64_t n_slots, void* stream);
+int fm_depth_standardize(const void* values_i32, int n_crops, int64_t n, int64_t lo, int64_t hi, void* out_f32, void* stats, void* stream);
+
+/* ---- lab(not part of the drop-in surface) ------------------------------------------------------------------------------------------
  * Experiment knobs of the GEMM kernels, used by tools/gemm_lab.cpp, the Python tools and the FOURM_NT3_LAB environment switch only: key 0 / 1
  * staggered workgroup start (groups, step), 2 gemm_nt3 mode override, 3 gemm_nt3 ablation flags (gemm_args.h NTArgs::lab), others reserved.
  * Process-global, not thread-safe, no effect on results except where an ablation flag says so.  Keys outside [0, 16) are ignored. */

@@ -1,7 +1,7 @@
 // Pillow-exact crop + resize + flip of 8-bit images over a device job list (include/fourm_hip.h, "Pillow-exact crops"): the data stage of
 // dataset pre-tokenization.  One job is one crop of one source image; many images of different sizes and all their crops go in one call.
 //
-// The arithmetic is Pillow's 8-bit path, integer from the coefficient tables on: fm_pil_axis_table (HOST, below) makes the table of one axis
+// The arithmetic is Pillow's 8-bit path, integer from the coefficient tables on: fm_pil_axis_table (HOST, pil_axis.h) makes the table of one axis
 // in double in Pillow's operation order - this file is compiled with -ffp-contract=off so that no multiply-add is contracted - and rounds
 // it to the 22-bit fixed-point coefficients Pillow uses.  The device side is two launches:
 //   rows:    every row of the crop is filtered along its columns into a uint8 intermediate (h, S, C) - Pillow's horizontal pass, its rounding
@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "fourm_hip.h"
+#include "pil_axis.h"
 
 namespace {
 
@@ -28,46 +29,7 @@ constexpr int NT = 256;
 constexpr long long MAX_BLOCKS = (1LL << 32) / NT - 1;          // a grid of 2^32 threads or more is rejected at launch
 constexpr int PRECISION_BITS = 22;          // Pillow's 32 - 8 - 2
 
-// ---- host: the table of one axis ------------------------------------------------------------------------------------------------------------
-inline double bilinear_filter(double x) {
-    if (x < 0.0) x = -x;
-    if (x < 1.0) return 1.0 - x;
-    return 0.0;
-}
-
-inline double bicubic_filter(double x) {
-    const double a = -0.5;
-    if (x < 0.0) x = -x;
-    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-    return 0.0;
-}
-
-// Row o of the table of n_in -> n_out: the doubles k (normalised) and the first input pixel.
-int filter_row(int n_in, int n_out, int filter, int o, std::vector<double>& k) {
-    const double scale = (double)n_in / n_out;
-    const double fs = scale < 1.0 ? 1.0 : scale;
-    const double support = (filter == FM_PIL_BICUBIC ? 2.0 : 1.0) * fs;
-    const double center = (o + 0.5) * scale;
-    const double ss = 1.0 / fs;
-    int xmin = (int)(center - support + 0.5);
-    if (xmin < 0) xmin = 0;
-    int xmax = (int)(center + support + 0.5);
-    if (xmax > n_in) xmax = n_in;
-    xmax -= xmin;
-    k.clear();
-    double ww = 0.0;
-    for (int x = 0; x < xmax; ++x) {
-        const double arg = (x + xmin - center + 0.5) * ss;
-        const double w = filter == FM_PIL_BICUBIC ? bicubic_filter(arg) : bilinear_filter(arg);
-        k.push_back(w);
-        ww += w;
-    }
-    for (double& v : k)
-        if (ww != 0.0) v /= ww;
-    return xmin;
-}
-
+// ---- host: the table of one axis (pil_axis.h; shared with the 16-bit path) -----------------------------------------------------------------------
 inline int32_t fixed_point(double k) {
     return k < 0 ? (int32_t)(-0.5 + k * (1 << PRECISION_BITS)) : (int32_t)(0.5 + k * (1 << PRECISION_BITS));
 }
@@ -178,40 +140,7 @@ inline bool aligned(const void* p, uintptr_t a) { return (((uintptr_t)p) & (a - 
 }  // namespace
 
 extern "C" int fm_pil_axis_table(int n_in, int n_out, int filter, int32_t* start, int32_t* count, int32_t* coef) {
-    FM_CHECK_ARG(n_in > 0 && n_out > 0 && n_in <= (1 << 24) && n_out <= (1 << 24), "fm_pil_axis_table: sizes %d -> %d (1 .. 2^24 each)", n_in, n_out);
-    FM_CHECK_ARG(filter == FM_PIL_NEAREST || filter == FM_PIL_BILINEAR || filter == FM_PIL_BICUBIC, "fm_pil_axis_table: filter %d", filter);
-    if (filter == FM_PIL_NEAREST || n_in == n_out) {          // one tap of weight 1: the affine scaler's index, or the identity of a pass that keeps its size
-        const double a = (double)n_in / n_out;
-        double xo = a * 0.5;
-        for (int o = 0; o < n_out; ++o) {
-            int idx = n_in == n_out ? o : (int)xo;
-            if (idx > n_in - 1) idx = n_in - 1;
-            if (start) start[o] = idx;
-            if (count) count[o] = 1;
-            if (coef) coef[o] = 1 << PRECISION_BITS;
-            xo += a;
-        }
-        return 1;
-    }
-    FM_CHECK_ARG((filter == FM_PIL_BICUBIC ? 4.0 : 2.0) * (double)n_in / (double)n_out + 1.0 <= (double)FM_PIL_MAX_TAPS || n_in <= FM_PIL_MAX_TAPS,
-                 "fm_pil_axis_table: %d -> %d needs windows wider than FM_PIL_MAX_TAPS = %d pixels", n_in, n_out, FM_PIL_MAX_TAPS);
-    std::vector<double> k;
-    int taps = 0;
-    for (int o = 0; o < n_out; ++o) {
-        const int xmin = filter_row(n_in, n_out, filter, o, k);
-        const int cnt = (int)k.size();
-        FM_CHECK_ARG(xmin >= 0 && cnt >= 0 && xmin + cnt <= n_in, "fm_pil_axis_table: window of output %d outside the input", o);
-        if (cnt > taps) taps = cnt;
-    }
-    FM_CHECK_ARG(taps >= 1 && taps <= FM_PIL_MAX_TAPS, "fm_pil_axis_table: %d -> %d has windows of %d pixels (1 .. %d)", n_in, n_out, taps, FM_PIL_MAX_TAPS);
-    for (int o = 0; o < n_out && (start || count || coef); ++o) {
-        const int xmin = filter_row(n_in, n_out, filter, o, k);
-        if (start) start[o] = xmin;
-        if (count) count[o] = (int)k.size();
-        if (coef)
-            for (int x = 0; x < taps; ++x) coef[(size_t)o * taps + x] = x < (int)k.size() ? fixed_point(k[x]) : 0;
-    }
-    return taps;
+    return pil_axis::table("fm_pil_axis_table", n_in, n_out, filter, false, start, count, coef, fixed_point);
 }
 
 extern "C" int fm_pil_crop_resize(const fm_pil_crop_job* jobs_host, const void* jobs_dev, int n_jobs, const void* src, int64_t src_bytes, const void* tables,

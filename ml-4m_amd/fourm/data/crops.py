@@ -7,6 +7,10 @@ and the crops themselves - ``PIL.Image.crop`` + ``Image.resize`` + horizontal fl
     make_crop_settings     the (n_crops, 5) array of save_vq_tokens.py:145-159: row 0 the unflipped centre crop, the rest random
     crop_resize            every crop of every image in one call: one pinned, packed host-to-device copy (job list, axis tables, lookup table,
                            image bytes), two launches
+    decode_depth           a 16-bit depth PNG (Pillow mode I;16) as uint16 (H, W)
+    crop_resize_depth      the same for depth maps: Pillow's 16-bit resample path (double accumulation, the clamp per byte) and upstream's
+                           truncated depth standardisation per crop (include/fourm_hip.h, "Pillow-exact 16-bit depth crops"; kernels in
+                           csrc/pil_resize16.hip)
 
 Workspaces (the pinned staging buffer, its device image and the intermediates) are kept per (device, stream) and grow to the largest call;
 a call waits for the previous upload from the same staging buffer before refilling it.  There is no CPU path."""
@@ -157,6 +161,25 @@ def _align(n, a):
     return (n + a - 1) // a * a
 
 
+def _boxes(images, settings):
+    """[(image, top, left, h, w, flip)] of every settings row, validated (ValueError) before the library sees a job."""
+    boxes = []
+    for i, (im, st) in enumerate(zip(images, settings)):
+        st = np.asarray(st)
+        if st.ndim != 2 or st.shape[1] != 5 or st.shape[0] < 1:
+            raise ValueError(f"settings {i}: (n, 5) rows of (top, left, h, w, flip) expected, got {st.shape}")
+        if not np.issubdtype(st.dtype, np.integer) and not np.array_equal(st, np.floor(st)):
+            raise ValueError(f"settings {i}: integers expected")
+        H, W = im.shape[:2]
+        for top, left, h, w, flip in st.astype(np.int64).tolist():
+            if not (h >= 1 and w >= 1 and top >= 0 and left >= 0 and top + h <= H and left + w <= W):
+                raise ValueError(f"image {i}: box (top {top}, left {left}, h {h}, w {w}) leaves the {H} x {W} image")
+            if flip not in (0, 1):
+                raise ValueError(f"image {i}: flip {flip} (0 or 1)")
+            boxes.append((i, top, left, h, w, flip))
+    return boxes
+
+
 def crop_resize(images, settings, size, resample=None, mean=None, std=None, invert_on_flip=(), out="float32"):
     """images: a list of uint8 (H, W, C) arrays or tensors of one channel count; settings: per image an (n_i, 5) array of rows
     (top, left, h, w, flip).  Returns the sum(n_i) crops at size x size in input order on the current device:
@@ -194,21 +217,7 @@ def crop_resize(images, settings, size, resample=None, mean=None, std=None, inve
         invert |= 1 << int(c)
     lut = normalize_lut(C, mean, std) if "float32" in outs else None
 
-    # the job list, validated here (ValueError) before the library sees it
-    boxes = []
-    for i, (im, st) in enumerate(zip(images, settings)):
-        st = np.asarray(st)
-        if st.ndim != 2 or st.shape[1] != 5 or st.shape[0] < 1:
-            raise ValueError(f"settings {i}: (n, 5) rows of (top, left, h, w, flip) expected, got {st.shape}")
-        if not np.issubdtype(st.dtype, np.integer) and not np.array_equal(st, np.floor(st)):
-            raise ValueError(f"settings {i}: integers expected")
-        H, W = im.shape[:2]
-        for top, left, h, w, flip in st.astype(np.int64).tolist():
-            if not (h >= 1 and w >= 1 and top >= 0 and left >= 0 and top + h <= H and left + w <= W):
-                raise ValueError(f"image {i}: box (top {top}, left {left}, h {h}, w {w}) leaves the {H} x {W} image")
-            if flip not in (0, 1):
-                raise ValueError(f"image {i}: flip {flip} (0 or 1)")
-            boxes.append((i, top, left, h, w, flip))
+    boxes = _boxes(images, settings)
     if not torch.cuda.is_available():
         raise RuntimeError("crop_resize runs on the HIP kernels only (an MI355X is needed; there is no CPU path)")
     device = torch.device("cuda", torch.cuda.current_device())
@@ -272,3 +281,158 @@ def crop_resize(images, settings, size, resample=None, mean=None, std=None, inve
                                   C, S, invert, C_.c_void_p(base + o_lut) if lut is not None else None, ptr(res.get("uint8")), ptr(res.get("float32")),
                                   ptr(res.get("int64")), N, C_.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
     return res[out] if isinstance(out, str) else tuple(res[o] for o in outs)
+
+
+# ---- 16-bit depth ---------------------------------------------------------------------------------------------------------------------------
+_TABLES_F64 = {}
+
+
+def decode_depth(path):
+    """A 16-bit depth PNG -> uint16 (H, W).  Pillow opens it as mode ``I;16``; any other mode (``I``, ``F``, big-endian ``I;16B``, an 8-bit
+    file) raises ValueError naming the mode: those do not go through Pillow's 16-bit resample path, which is the one restated here."""
+    from PIL import Image
+    with Image.open(path) as img:
+        if img.mode != "I;16":
+            raise ValueError(f"{path}: mode {img.mode!r}, expected a 16-bit grayscale image (mode 'I;16')")
+        W, H = img.size
+        return np.frombuffer(img.tobytes(), dtype="<u2").reshape(H, W).astype(np.uint16)
+
+
+def pil_axis_table_f64(n, S, filt):
+    """fm_pil_axis_table_f64 on the host -> one int32 array of S (2 + 2 taps) words, start (S) | count (S) | coef float64 (S, taps), and taps.
+    Cached per (n, S, filter)."""
+    import ctypes as C
+    from fourm.hip import _lib as L
+    key = (int(n), int(S), filt)
+    hit = _TABLES_F64.get(key)
+    if hit is not None:
+        return hit
+    fid = _FILTER_ID[filt]
+    taps = L.pil_axis_table_f64(key[0], key[1], fid, None, None, None)
+    if taps < 1:
+        L.check(-1)
+    tab = np.zeros(key[1] * (2 + 2 * taps), np.int32)
+    P = C.POINTER(C.c_int32)
+    base = tab.ctypes.data
+    if L.pil_axis_table_f64(key[0], key[1], fid, C.cast(base, P), C.cast(base + 4 * key[1], P), C.cast(base + 8 * key[1], C.POINTER(C.c_double))) != taps:
+        L.check(-1)
+    if len(_TABLES_F64) >= _TABLES_MAX:
+        _TABLES_F64.clear()
+    _TABLES_F64[key] = (tab, taps)
+    return tab, taps
+
+
+def _as_hw16(img, i):
+    if isinstance(img, torch.Tensor):
+        img = img.detach().cpu().numpy()
+    img = np.asarray(img)
+    if img.dtype != np.uint16:
+        raise TypeError(f"image {i}: uint16 expected, got {img.dtype}")
+    if img.ndim == 3 and img.shape[2] == 1:
+        img = img[:, :, 0]
+    if img.ndim != 2 or img.shape[0] < 1 or img.shape[1] < 1:
+        raise ValueError(f"image {i}: (H, W) expected, got {img.shape}")
+    return np.ascontiguousarray(img)
+
+
+def crop_resize_depth(images, settings, size, resample=None, standardize=True, out="float32", return_stats=False):
+    """images: a list of uint16 (H, W) depth maps (``decode_depth``); settings: per image an (n_i, 5) array of rows (top, left, h, w, flip),
+    as for ``crop_resize``.  Returns the sum(n_i) crops at size x size in input order on the current device, as Pillow's 16-bit resample
+    path and upstream's DepthTransform make them (include/fourm_hip.h, "Pillow-exact 16-bit depth crops"):
+
+        out="uint16"   int32 (N, size, size): Pillow's 16-bit values (torch has no arithmetic on uint16)
+        out="float32"  float32 (N, 1, size, size): v / 65535, and with standardize=True upstream's truncated_depth_standardization of
+                       each crop: (x - mean) / sqrt(var + 1e-6), mean and unbiased variance over the sorted ranks int(0.1 n) .. int(0.9 n) - 1
+        a tuple of these names returns a tuple of tensors from the same launches.
+
+    return_stats=True (standardize=True only) appends the float32 (N, 2) tensor of (mean, var) per crop.  The same errors before any launch
+    as ``crop_resize``; size < 2 with standardize=True raises ValueError (the truncated range has fewer than two elements)."""
+    import ctypes as C_
+    from fourm.hip import _lib as L
+    if resample not in RESAMPLE:
+        raise ValueError(f"resample {resample!r}: one of {list(RESAMPLE)}")
+    filt = RESAMPLE[resample]
+    outs = (out,) if isinstance(out, str) else tuple(out)
+    if not outs or any(o not in ("float32", "uint16") for o in outs) or len(set(outs)) != len(outs):
+        raise ValueError(f"out {out!r}: 'float32', 'uint16' or a tuple of them")
+    S = int(size)
+    if not 1 <= S <= 16384:
+        raise ValueError(f"size {size}: 1 .. 16384")
+    standardize = bool(standardize) and "float32" in outs
+    n = S * S
+    lo, hi = int(0.1 * n), int((1 - 0.1) * n)          # upstream's slice bounds, in Python doubles
+    if standardize and hi - lo < 2:
+        raise ValueError(f"size {size}: the truncated range [{lo}, {hi}) of {n} values has fewer than two elements (standardize=True needs size >= 2)")
+    if return_stats and not standardize:
+        raise ValueError("return_stats=True needs standardize=True and out 'float32'")
+    images = [_as_hw16(im, i) for i, im in enumerate(images)]
+    if len(images) == 0 or len(images) != len(settings):
+        raise ValueError(f"{len(images)} images and {len(settings)} settings: one settings array per image, at least one image")
+
+    boxes = _boxes(images, settings)
+    if not torch.cuda.is_available():
+        raise RuntimeError("crop_resize_depth runs on the HIP kernels only (an MI355X is needed; there is no CPU path)")
+    device = torch.device("cuda", torch.cuda.current_device())
+
+    # the packed buffer: jobs | tables | images
+    N = len(boxes)
+    jobs = (L.PilCropJob * N)()
+    tab_off, tabs, words = {}, [], 0
+    for m in sorted({b[4] for b in boxes} | {b[3] for b in boxes}):
+        tab, taps = pil_axis_table_f64(m, S, filt)
+        tab_off[m] = (words, taps)
+        tabs.append(tab)
+        words += tab.size          # S (2 + 2 taps): even, the doubles stay 8-byte aligned
+    if words >= 1 << 31:
+        raise ValueError("axis tables too large")
+    src_off, nbytes = [], 0
+    for im in images:
+        src_off.append(nbytes)
+        nbytes += 2 * im.size
+    mid_bytes = blk_rows = blk_cols = 0
+    per_cols = (S * S + 255) // 256
+    for k, (i, top, left, h, w, flip) in enumerate(boxes):
+        j = jobs[k]
+        j.src_off, j.mid_off, j.out_slot, j.blk_rows, j.blk_cols = src_off[i], mid_bytes, k, blk_rows, blk_cols
+        j.H, j.W = images[i].shape
+        j.top, j.left, j.h, j.w, j.flip = top, left, h, w, flip
+        (j.tab_w, j.taps_w), (j.tab_h, j.taps_h) = tab_off[w], tab_off[h]
+        mid_bytes += 2 * h * S
+        blk_rows += (h * S + 255) // 256
+        blk_cols += per_cols
+    o_jobs = 0
+    o_tab = _align(C_.sizeof(jobs), 16)
+    o_img = _align(o_tab + 4 * words, 16)
+    total = o_img + nbytes
+    ws = _workspace(device)
+    host, dev = ws.staging(total, device)
+    hv = host.numpy()
+    hv[o_jobs:o_jobs + C_.sizeof(jobs)] = np.frombuffer(jobs, dtype=np.uint8)
+    hv[o_tab:o_tab + 4 * words] = np.concatenate(tabs).view(np.uint8)
+    for im, off in zip(images, src_off):
+        hv[o_img + off:o_img + off + 2 * im.size] = im.reshape(-1).view(np.uint8)
+    dev[:total].copy_(host[:total], non_blocking=True)
+    ws.done = torch.cuda.Event()
+    ws.done.record(torch.cuda.current_stream(device))
+    mid = ws.scratch(mid_bytes, device)
+
+    res = {}
+    need_values = "uint16" in outs or standardize          # the standardisation reads the integer values
+    values = torch.empty(N, S, S, dtype=torch.int32, device=device) if need_values else None
+    if "uint16" in outs:
+        res["uint16"] = values
+    if "float32" in outs:
+        res["float32"] = torch.empty(N, 1, S, S, dtype=torch.float32, device=device)
+    stats = torch.empty(N, 2, dtype=torch.float32, device=device) if return_stats else None
+    base = dev.data_ptr()
+    ptr = lambda t: C_.c_void_p(t.data_ptr()) if t is not None else None
+    stream = C_.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    with torch.cuda.device(device):
+        L.check(L.pil_crop_resize16(jobs, C_.c_void_p(base + o_jobs), N, C_.c_void_p(base + o_img), nbytes, C_.c_void_p(base + o_tab), words, ptr(mid), mid.numel(),
+                                    S, ptr(values), None if standardize else ptr(res.get("float32")), N, stream))
+        if standardize:
+            L.check(L.depth_standardize(ptr(values), N, n, lo, hi, ptr(res["float32"]), ptr(stats), stream))
+    got = tuple(res[o] for o in outs)
+    if return_stats:
+        return (*got, stats)
+    return got[0] if isinstance(out, str) else got
