@@ -1075,6 +1075,37 @@ int fm_pil_crop_resize16(const fm_pil_crop_job* jobs_host, const void* jobs_dev,
                          int64_t table_words, void* scratch, int64_t scratch_bytes, int S, void* out_i32, void* out_f32, int64_t n_slots, void* stream);
 int fm_depth_standardize(const void* values_i32, int n_crops, int64_t n, int64_t lo, int64_t hi, void* out_f32, void* stats, void* stream);
 
+/* CLIP text tower and CLIP score (csrc/clip_text.hip): the two ends of upstream's CLIP.encode_text / CLIP.forward (fourm/utils/clip/model.py
+ * :407-440) that the trunk's kernels do not cover.  The blocks between them are the trunk's (LayerNorm, qkv GEMM, fm_attn_fwd / fm_attn_f32_fwd
+ * with FM_MASK_DECODER and causal = 1, cs = modq = modk = NULL: blocked[q][k] = k > q, upstream's triu(1) mask; FM_EPI_QUICK_GELU).  Everything
+ * here is fp32 and row-local: one wavefront owns a row, lane l accumulates elements l, l + 64, ... in index order, then the shuffle tree.  No
+ * floating-point atomics: two calls on the same inputs give the same bits.  The normalisation of a finished fp32 sum (square roots, division)
+ * is evaluated in double and rounded to fp32 once.
+ * The entry points were ADDED without raising FM_ABI_VERSION (it stays 11); a caller that needs them checks for the symbols.
+ *
+ * fm_clip_text_embed: ids int64 (B, Lc) contiguous; token_embedding f32 (V, D); positional_embedding f32 (Lc, D); both contiguous, 16-byte
+ *   aligned.  out f32 rows with row stride ldo: out[b Lc + t] = token_embedding[ids[b][t]] + positional_embedding[t], one fp32 add per element.
+ *   eot_row int32 (B): b Lc + argmax_t ids[b][t], the FIRST maximum on ties (torch.argmax) - the row CLIP.encode_text projects.  eot_map
+ *   int32 (B Lc), optional (may be NULL): the same pick as a row map of fm_layernorm_fwd - b at the end-of-text row of sample b, -1 at every
+ *   other row - so that ln_final normalises exactly the B rows that are projected, without a gather in between.  An id outside
+ *   [0, V) is never used as an index: its row is written as zeros and counted.  bad int32 (1): zeroed by the call, then the number of such ids
+ *   (an integer atomic; the order cannot matter).  D and ldo multiples of 4.
+ * fm_clip_pair_score: img f32 (B, E) with row stride ldi, txt f32 (B, E) with row stride ldt.  score f32 (B): 100 <img_b, txt_b> / (|img_b|
+ *   |txt_b|) - dot product and squared norms accumulated in fp32 in the order above, 100 dot / (sqrt(n_i) sqrt(n_t)) in double, rounded once;
+ *   a pair with a zero norm scores 0, not NaN.  sum f64 (1) += the sum of the B scores: every workgroup (4 pairs) leaves ((s0 + s1) + s2) + s3
+ *   as one double in scratch (fm_clip_pair_score_scratch doubles; that function returns the count, or -1), a second launch adds the partials
+ *   in index order.  count int64 (1) += B (may be NULL).  sum and count are ACCUMULATORS in device memory: the caller zeroes them.
+ * fm_l2_normalize_rows: y[r] = x[r] * (f / |x[r]|), f = factor * (factor_dev ? factor_dev[0] : 1) with factor_dev f32 (1) in device memory or
+ *   NULL; f / sqrt(sum of squares) in double, rounded to fp32 once, then one fp32 multiply per element.  A zero row stays zero.  x == y (in
+ *   place) is allowed.  f32 rows (R, E) with row strides ldx, ldy.
+ * Refused (-1) before anything is written: null or misaligned pointers, non-positive sizes, a row stride below the row length. */
+int fm_clip_text_embed(const void* ids, const void* token_embedding, const void* positional_embedding, void* out, int ldo, void* eot_row,
+                       void* eot_map, void* bad, int B, int Lc, int D, int V, void* stream);
+int fm_clip_pair_score_scratch(int B);
+int fm_clip_pair_score(const void* img, int ldi, const void* txt, int ldt, void* score, void* scratch, void* sum, void* count, int B, int E,
+                       void* stream);
+int fm_l2_normalize_rows(const void* x, int ldx, void* y, int ldy, int R, int E, const void* factor_dev, float factor, void* stream);
+
 /* ---- lab(not part of the drop-in surface) ------------------------------------------------------------------------------------------
  * Experiment knobs of the GEMM kernels, used by tools/gemm_lab.cpp, the Python tools and the FOURM_NT3_LAB environment switch only: key 0 / 1
  * staggered workgroup start (groups, step), 2 gemm_nt3 mode override, 3 gemm_nt3 ablation flags (gemm_args.h NTArgs::lab), others reserved.

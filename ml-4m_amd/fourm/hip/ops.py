@@ -949,3 +949,43 @@ def resize_nearest(x, y, index_h, index_w):
     assert index_h.numel() == Ho and index_w.numel() == Wo
     L.check(L.resize_nearest(_p(x), _p(y), x.element_size(), x.numel() // (Hi * Wi), Hi, Wi, Ho, Wo, _p(index_h), _p(index_w), _stream()))
     return y
+
+
+# ---------------------------------------------------------------------------------------------
+# CLIP text tower and CLIP score (csrc/clip_text.hip)
+# ---------------------------------------------------------------------------------------------
+def clip_text_embed(ids, tok, pos, out, eot_row, bad, eot_map=None):
+    """out[b Lc + t] = tok[ids[b, t]] + pos[t] (f32 rows), eot_row (B,) int32 = b Lc + argmax_t ids[b, t] (first maximum), eot_map (B Lc,) int32
+    (optional) = the same pick as a LayerNorm row map, bad (1,) int32 = ids outside the table (their rows are zeros) - fm_clip_text_embed."""
+    B, Lc = ids.shape
+    V, D = tok.shape
+    assert ids.dtype == torch.int64 and ids.is_contiguous() and tok.dtype == pos.dtype == out.dtype == torch.float32 and tok.is_contiguous() and pos.is_contiguous()
+    assert tuple(pos.shape) == (Lc, D) and out.dim() == 2 and out.shape[0] >= B * Lc and out.shape[1] >= D
+    assert eot_row.dtype == torch.int32 and eot_row.numel() == B and bad.dtype == torch.int32 and bad.numel() == 1
+    assert eot_map is None or (eot_map.dtype == torch.int32 and eot_map.numel() == B * Lc and eot_map.is_contiguous())
+    with _prof("clip_text_embed", 0.0, 8.0 * B * Lc * D):
+        L.check(L.clip_text_embed(_p(ids), _p(tok), _p(pos), _p(out), _ld(out), _p(eot_row), _p(eot_map), _p(bad), B, Lc, D, V, _stream()))
+    return out
+
+
+def clip_pair_score(img, txt, score, total, count=None):
+    """score (B,) f32 = 100 cos(img[b], txt[b]); total (1,) f64 += their sum (fixed order), count (1,) int64 += B - fm_clip_pair_score."""
+    B, E = img.shape
+    assert img.dtype == txt.dtype == score.dtype == torch.float32 and tuple(txt.shape) == (B, E) and img.stride(1) == 1 and txt.stride(1) == 1
+    assert score.numel() == B and score.is_contiguous() and total.dtype == torch.float64 and total.numel() == 1
+    assert count is None or (count.dtype == torch.int64 and count.numel() == 1)
+    n = L.clip_pair_score_scratch(B)
+    L.check(min(n, 0))
+    scratch = torch.empty(n, dtype=torch.float64, device=img.device)
+    L.check(L.clip_pair_score(_p(img), img.stride(0), _p(txt), txt.stride(0), _p(score), _p(scratch), _p(total), _p(count), B, E, _stream()))
+    return score
+
+
+def l2_normalize_rows(x, y=None, factor=1.0, factor_dev=None):
+    """y[r] = x[r] * factor * factor_dev[0] / |x[r]| for f32 rows (R, E); y None: in place; a zero row stays zero - fm_l2_normalize_rows."""
+    y = x if y is None else y
+    R, E = x.shape
+    assert x.dtype == y.dtype == torch.float32 and tuple(y.shape) == (R, E) and x.stride(1) == 1 and y.stride(1) == 1
+    assert factor_dev is None or (factor_dev.dtype == torch.float32 and factor_dev.numel() == 1)
+    L.check(L.l2_normalize_rows(_p(x), x.stride(0), _p(y), y.stride(0), R, E, _p(factor_dev), float(factor), _stream()))
+    return y

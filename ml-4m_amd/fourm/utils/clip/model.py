@@ -11,8 +11,8 @@ forward is a launch sequence on one MI355X, inference only:
 
 ``compute_precision`` "bf16" (default) is upstream's autocast arithmetic: bf16 GEMM operands, fp32 accumulation, fp32 residual stream,
 LayerNorm statistics and softmax.  "fp32" runs the same sequence on the fp32 kernels (csrc/fp32_verify.hip): upstream's run without
-autocast.  Every result is fp32.  ``CLIP``, ``ModifiedResNet``, the text tower, ``build_model`` and ``clip.load`` stay upstream's
-(fourm/_upstream.py); ``VisionTransformer.from_upstream(model.visual)`` adopts a loaded tower.
+autocast.  Every result is fp32.  ``CLIP``, ``ModifiedResNet``, ``build_model`` and ``clip.load`` stay upstream's (fourm/_upstream.py; the
+text tower is fourm/utils/clip/text.py); ``VisionTransformer.from_upstream(model.visual)`` adopts a loaded tower.
 
 ``features`` / ``features_backward`` are the differentiable path of a FROZEN tower: the residual streams after chosen blocks and the gradient of
 anything computed from them with respect to the input image (the perceptual loss of tokenizer training, fourm/vq/percept_losses).  ``forward``

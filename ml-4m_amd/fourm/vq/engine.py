@@ -106,8 +106,9 @@ def _pos_rows(eng, vit, B, nh, nw, Rp):
     return pos
 
 
-def _blocks_fwd(eng, vit, stream, B, G, st, prefix):
-    none = dict(mask_kind=L.MASK_NONE)
+def _blocks_fwd(eng, vit, stream, B, G, st, prefix, mask=None):
+    """``mask`` (attention keywords of ops.attn_fwd, e.g. CLIP's causal text tower: fourm/utils/clip/text.py): replaces the unmasked default."""
+    none = dict(mask_kind=L.MASK_NONE) if mask is None else mask
     for i, blk in enumerate(vit.blocks):
         sv = {} if st is not None else None
         # (the last residual sum of every block but the final one is left to the next block's norm1: a bf16 GEMM + fm_layernorm_fwd_res)
