@@ -1106,6 +1106,50 @@ int fm_clip_pair_score(const void* img, int ldi, const void* txt, int ldt, void*
                        void* stream);
 int fm_l2_normalize_rows(const void* x, int ldx, void* y, int ldy, int R, int E, const void* factor_dev, float factor, void* stream);
 
+/* Flat k-NN index (csrc/knn.hip): the exact top-k search of nq query rows against n gallery rows of width d, everything fp32 - the search step
+ * of 4M-21's retrieval (upstream: faiss.IndexFlatL2 / IndexFlatIP).  No score matrix goes to memory and there are no floating-point atomics.
+ * The entry points were ADDED without raising FM_ABI_VERSION (it stays 11); a caller that needs them checks for the symbols.
+ *
+ * Score: s(q, x) = sum_i q_i x_i on v_mfma_f32_32x32x2_f32, ONE fp32 accumulation chain over i ascending.  It is a function of (query row,
+ *   gallery row, d): the same bits wherever the gallery row sits and whatever nq, k, splits, query_tile or the batch are.
+ * Key: FM_KNN_IP: s, larger is better.  FM_KNN_L2: kappa = fmaf(-2, s, |x|^2), smaller is better, with |x|^2 the fp32 row sum of
+ *   fm_row_sqnorms (made once, in a fixed order); |q|^2 is constant per query and is left out.
+ * Order: total, on (key, gallery index): better key first, lower index first on equal keys (-0 and +0 are equal).  The result is the first
+ *   k of that order, so it does not depend on the split or on the order in which candidates were met.  Fewer than k gallery rows: the
+ *   missing slots are index -1 with distance +inf (FM_KNN_L2) / -inf (FM_KNN_IP).  NaN inputs are not supported.
+ * Split: the gallery is cut into `splits` chunks of per = ceil(ceil(n / 128) / splits) tiles of 128 rows (chunk c: rows [128 per c,
+ *   128 per (c + 1)), the last ones possibly empty).  A workgroup owns (query tile, chunk), keeps a running top-k per query row in LDS and
+ *   leaves k candidates per (query, chunk) in scratch; a merge workgroup per query sorts the splits k candidates.  splits k <=
+ *   FM_KNN_MAX_MERGE.  fm_knn_splits proposes a count from nq, n, k and the CU count (a single query over a long gallery still fills the chip).
+ * Query tile: 128 queries per workgroup, or 32 (a quarter of the matrix work per gallery byte: for a few queries the search is bound by the
+ *   gallery read).  query_tile = 0 picks by nq (fm_knn_query_tile: 32 up to 64 queries).  Both give the same bits.
+ * Sizes: 1 <= n <= 2^31 - 1 (offsets into the gallery are 64-bit), d a multiple of 4 up to FM_KNN_MAX_D, rows contiguous (row stride d) and
+ *   16-byte aligned, 1 <= k <= FM_KNN_MAX_K, at most 65535 query tiles per call.
+ *
+ * fm_row_sqnorms: out f32 (n) = |x_r|^2 of x f32 (n, d): a wavefront per row, lane l adds elements 4 l .. 4 l + 3, 4 l + 256 .. in index
+ *   order (fmaf), then the shuffle tree.
+ * fm_knn_query_tile, fm_knn_splits, fm_knn_scratch_bytes: HOST functions, no GPU call.  The query tile chosen for nq; the proposed split count
+ *   (cus = the device's compute units); *bytes = nq splits k 8.  -1 on a bad argument.
+ * fm_knn_search: q f32 (nq, d), x f32 (n, d), xnorm f32 (n) (FM_KNN_L2; may be NULL for FM_KNN_IP), scratch caller-owned (scratch_bytes).
+ *   out_d f32 (nq, k): the keys (s or kappa), best first;  out_i int64 (nq, k).  Two launches.
+ * fm_knn_refine_l2: for the indices i_io int64 (nq, k) of an FM_KNN_L2 search: delta = sum_i (q_i - x_i)^2 in fp32 (the same lane order as
+ *   fm_row_sqnorms; the terms are non-negative, no cancellation), the k entries re-ordered by (delta, index) in place, d_io f32 (nq, k) =
+ *   delta.  An index outside [0, n) is never used as an offset: it is padding (-1, +inf) and goes last.
+ * Refused (-1) before anything is launched or written: null or misaligned pointers, sizes outside the ranges above, an unknown metric or
+ *   query tile, a scratch smaller than fm_knn_scratch_bytes.  No allocation, no host synchronisation. */
+#define FM_KNN_IP 0
+#define FM_KNN_L2 1
+#define FM_KNN_MAX_K 64
+#define FM_KNN_MAX_D 4096
+#define FM_KNN_MAX_MERGE 4096
+int fm_row_sqnorms(const void* x, int n, int d, void* out, void* stream);
+int fm_knn_query_tile(int nq);
+int fm_knn_splits(int nq, int n, int k, int cus);
+int fm_knn_scratch_bytes(int nq, int k, int splits, int64_t* bytes);
+int fm_knn_search(const void* q, int nq, const void* x, const void* xnorm, int n, int d, int k, int metric, int splits, int query_tile,
+                  void* scratch, int64_t scratch_bytes, void* out_d, void* out_i, void* stream);
+int fm_knn_refine_l2(const void* q, int nq, const void* x, int n, int d, int k, void* d_io, void* i_io, void* stream);
+
 /* ---- lab(not part of the drop-in surface) ------------------------------------------------------------------------------------------
  * Experiment knobs of the GEMM kernels, used by tools/gemm_lab.cpp, the Python tools and the FOURM_NT3_LAB environment switch only: key 0 / 1
  * staggered workgroup start (groups, step), 2 gemm_nt3 mode override, 3 gemm_nt3 ablation flags (gemm_args.h NTArgs::lab), others reserved.
