@@ -108,46 +108,70 @@ NT_TILED = 9 + 256                   # automatic configuration, tile-at-a-time k
 NT_FLAT = 9 + 256 + (1 << 29)        # + the flattened persistent kernel where it applies
 
 
+def _dense_route(M, N, K, epi="bf16", **kw):
+    """The kernel fm_gemm_nt picks for a contiguous launch (tests/gemm_f64_util.py restates the dispatch; tests/test_gemm_ref_cpu.py checks it)."""
+    from tests.gemm_f64_util import lends_splitk, nt_route
+    return nt_route(M, N, K, epi, splitk_ws_bytes=lends_splitk(M, N, K, epi), cus=torch.cuda.get_device_properties(0).multi_processor_count, **kw)
+
+
+FLAT_LAB_OFF = {2: 0, 4: 0, 9: 0}    # gemm_nt3, gemm_nt4 and the small-grid policy sit in front of the flat kernel in fm_gemm_nt: off for both runs
+LAB_DEFAULTS = {2: 3, 4: 1, 9: 1}
+
+
 @pytest.mark.parametrize("M,N,K", [(32768, 768, 768), (6000, 2304, 768), (2048, 128, 512), (4100, 768, 4096), (33000, 1536, 1024)])
 def test_gemm_nt_flat_bit_identical(M, N, K):
     """The flattened persistent kernel (gemm_nt_flat.hip: one K-tile stream across all tiles of a workgroup, deferred
     stores) accumulates in the same order as the tile-at-a-time kernels: outputs must be bit-identical, run after run (a race
-    in the staggered LDS ring or a miscounted vmcnt wait would show as rare wrong tiles), and right against fp32."""
+    in the staggered LDS ring or a miscounted vmcnt wait would show as rare wrong tiles), and right against fp32.
+    gemm_nt3 / gemm_nt4 (fm_lab_set 2, 4) and the small-grid policy (fm_lab_set 9) are off for both runs - with them on, neither run
+    reaches the kernels this test compares: the reference is the tile-at-a-time kernel of gemm.hip, the run the flat kernel."""
     ops, L = _ops()
     x = bf(randn(M, K, seed=21) * 0.7)
     w = bf(randn(N, K, seed=22) * 0.05)
-    L.lib.fm_set_gemm_nt_config(NT_TILED)
-    ref = torch.full((M, N), 5.0, device=DEV, dtype=torch.bfloat16)
-    ops.gemm_nt(x, w, ref)
-    rows = torch.randperm(M, device=DEV)[:512]
-    assert rel_err(ref[rows], x[rows].float() @ w.float().t()) < 4e-3
-    L.lib.fm_set_gemm_nt_config(NT_FLAT)
+    assert _dense_route(M, N, K, ldo=N, lab=FLAT_LAB_OFF).startswith("tiled.cfg")
+    assert _dense_route(M, N, K, ldo=N, lab=FLAT_LAB_OFF, nt_config=NT_FLAT) == "flat.bf16"
     try:
+        for k, v in FLAT_LAB_OFF.items():
+            L.lib.fm_lab_set(k, v)
+        L.lib.fm_set_gemm_nt_config(NT_TILED)
+        ref = torch.full((M, N), 5.0, device=DEV, dtype=torch.bfloat16)
+        ops.gemm_nt(x, w, ref)
+        rows = torch.randperm(M, device=DEV)[:512]
+        assert rel_err(ref[rows], x[rows].float() @ w.float().t()) < 4e-3
+        L.lib.fm_set_gemm_nt_config(NT_FLAT)
         for rep in range(6):
             out = torch.full((M, N), -3.0, device=DEV, dtype=torch.bfloat16)
             ops.gemm_nt(x, w, out)
             assert torch.equal(out, ref), (rep, int((out != ref).sum()))
     finally:
         L.lib.fm_set_gemm_nt_config(NT_TILED)
+        for k, v in LAB_DEFAULTS.items():
+            L.lib.fm_lab_set(k, v)
 
 
 @pytest.mark.parametrize("M,H,K,save", [(32768, 2048, 768, True), (5000, 448, 768, True), (4096, 2048, 768, False)])
 def test_gemm_nt_flat_swiglu_bit_identical(M, H, K, save):
+    """As above for the SwiGLU epilogue (gemm_nt3 / gemm_nt4 off for both runs: tile-at-a-time kernel against the flat one)."""
     ops, L = _ops()
     x, w1, w3 = bf(randn(M, K, seed=23) * 0.7), bf(randn(H, K, seed=24) * 0.05), bf(randn(H, K, seed=25) * 0.05)
+    kw = dict(out2=save, ldo=H, ldo2=2 * H if save else 0, Hp=H, lab=FLAT_LAB_OFF)
+    assert _dense_route(M, H, K, "swiglu", **kw).startswith("tiled.swiglu")
+    assert _dense_route(M, H, K, "swiglu", nt_config=NT_FLAT, **kw) == "flat.swiglu"
 
     def run():
         gu = torch.full((M, 2 * H), 3.0, device=DEV, dtype=torch.bfloat16) if save else None
         act = torch.full((M, H), 3.0, device=DEV, dtype=torch.bfloat16)
         ops.gemm_nt(x, w1, act, epilogue=L.EPI_SWIGLU, w2=w3, out2=gu, Hp=H, N=H)
         return act, gu
-    L.lib.fm_set_gemm_nt_config(NT_TILED)
-    act0, gu0 = run()
-    rows = torch.randperm(M, device=DEV)[:256]
-    g, u = bf(x[rows].float() @ w1.float().t()).float(), bf(x[rows].float() @ w3.float().t()).float()
-    assert rel_err(act0[rows], bf(torch.nn.functional.silu(g)).float() * u) < 8e-3
-    L.lib.fm_set_gemm_nt_config(NT_FLAT)
     try:
+        for k, v in FLAT_LAB_OFF.items():
+            L.lib.fm_lab_set(k, v)
+        L.lib.fm_set_gemm_nt_config(NT_TILED)
+        act0, gu0 = run()
+        rows = torch.randperm(M, device=DEV)[:256]
+        g, u = bf(x[rows].float() @ w1.float().t()).float(), bf(x[rows].float() @ w3.float().t()).float()
+        assert rel_err(act0[rows], bf(torch.nn.functional.silu(g)).float() * u) < 8e-3
+        L.lib.fm_set_gemm_nt_config(NT_FLAT)
         for rep in range(4):
             act, gu = run()
             assert torch.equal(act, act0), rep
@@ -155,18 +179,30 @@ def test_gemm_nt_flat_swiglu_bit_identical(M, H, K, save):
                 assert torch.equal(gu, gu0), rep
     finally:
         L.lib.fm_set_gemm_nt_config(NT_TILED)
+        for k, v in LAB_DEFAULTS.items():
+            L.lib.fm_lab_set(k, v)
 
 
 @pytest.mark.parametrize("M,N,K", [(32768, 768, 768), (4096, 2304, 768), (2048, 1536, 1024), (8192, 768, 4096), (2304, 384, 192), (6144, 768, 2048)])
-@pytest.mark.parametrize("mode", [1, 5])
+@pytest.mark.parametrize("mode", [1, 5, 9, 13])
 def test_gemm_nt4_bit_identical(M, N, K, mode):
     """The 4-wave 256 x 384-tile kernel (gemm_nt4.hip: 16 accumulator fragments in hand-named AGPRs, staged whole-line epilogue through the stage
-    buffer a tile's last barrier freed; mode 5 = unstaged stores) accumulates in gemm_nt3's order: bit-identical outputs, run after run, and right
-    against fp32.  One / several tiles per workgroup, K from 3 K-tiles up."""
+    buffer a tile's last barrier freed; mode bit 2 = unstaged stores) accumulates in gemm_nt3's order: bit-identical outputs, run after run, and
+    right against fp32.  One / several tiles per workgroup, K from 3 K-tiles up.
+    Modes 9 and 13 (bit 3: take the launch whatever the rounds) run gemm_nt4 at ALL six shapes.  Modes 1 and 5 apply fm_launch_nt4's cost
+    rule, which on 256 CUs accepts (32768, 768, 768) alone: at (4096, 2304, 768), (2048, 1536, 1024), (8192, 768, 4096), (2304, 384, 192) and
+    (6144, 768, 2048) both runs are gemm_nt3's and the comparison holds trivially.  The small-grid policy (fm_lab_set 9), which would take
+    four of the shapes in front of either kernel, is off for the reference and for the run."""
+    from tests.gemm_f64_util import nt4_takes
     ops, L = _ops()
     x = bf(randn(M, K, seed=31) * 0.7 + torch.arange(K, device=DEV)[None] * 0.001)
     w = bf(randn(N, K, seed=32) * 0.05 + torch.arange(N, device=DEV)[:, None] * 0.0001)
+    if mode & 8:
+        assert nt4_takes(M, N, K, mode) is not None
+        assert _dense_route(M, N, K, ldo=N, lab={9: 0, 4: mode}).startswith("nt4.384")
+    assert _dense_route(M, N, K, ldo=N, lab={9: 0, 4: 0}).startswith("nt3.")
     try:
+        L.lib.fm_lab_set(9, 0)
         L.lib.fm_lab_set(4, 0)
         ref = torch.full((M, N), 5.0, device=DEV, dtype=torch.bfloat16)
         ops.gemm_nt(x, w, ref)
@@ -185,6 +221,7 @@ def test_gemm_nt4_bit_identical(M, N, K, mode):
         assert torch.equal(big[:, 128:128 + N], ref) and bool((big[:, :128] == 9.0).all()) and bool((big[:, 128 + N:] == 9.0).all())
     finally:
         L.lib.fm_lab_set(4, 1)
+        L.lib.fm_lab_set(9, 1)
 
 
 @pytest.mark.parametrize("M,N,K", [(128, 128, 64), (256, 384, 128), (300, 260, 192), (1024, 768, 768), (70, 2304, 768)])
