@@ -1150,6 +1150,57 @@ int fm_knn_search(const void* q, int nq, const void* x, const void* xnorm, int n
                   void* scratch, int64_t scratch_bytes, void* out_d, void* out_i, void* stream);
 int fm_knn_refine_l2(const void* q, int nq, const void* x, int n, int d, int k, void* d_io, void* i_io, void* stream);
 
+/* Inception tower (csrc/inception.hip): the kernels behind FID and the Inception score (fourm/utils/inception) - the FID variant of
+ * InceptionV3 in fp32, as torchmetrics runs it.  Everything is fp32 NHWC "rows": a feature map of B images is a matrix (B H W, ld) with the
+ * channels of a pixel contiguous and ld >= C floats between pixels, so a concatenation is written as channel slices of one buffer (the
+ * caller passes out + c0).  No floating-point atomics: every output element is written once, in a summation order that depends on the
+ * element alone, so two calls give the same bits.  The entry points were ADDED without raising FM_ABI_VERSION (it stays 11).
+ *
+ * fm_conv2d_nhwc_f32: out[b, oy, ox, n] = act(bias[n] + acc), acc = ONE fp32 accumulation chain, starting from 0, over
+ *   k = (ky KW + kx) Cin + c ascending of x[b, oy stride - pad_h + ky, ox stride - pad_w + kx, c] * w[n, k]; taps outside the image contribute
+ *   x = 0 (zero padding).  Ho = (H + 2 pad_h - KH) / stride + 1, Wo likewise.  x: f32 rows (B H W, ldx); w: f32 (Cout, KH KW Cin), tap-major and
+ *   channel-minor, row stride ldw; bias: f32 (Cout) or NULL (zeros); out: f32 rows (B Ho Wo, ldo) at the pointer given; columns outside
+ *   [0, Cout) of a row are never written.  act = ReLU when relu != 0.  KH, KW in 1..FM_CONV2D_MAX_K, stride 1 | 2 (both axes), pad_h, pad_w in
+ *   0..FM_CONV2D_MAX_PAD, any Cin, Cout >= 1, fewer than 2^31 input and output rows.  Implicit GEMM on v_mfma_f32_32x32x2_f32 (exact fp32, an fmaf
+ *   chain over k): the activation tile is gathered into LDS with bounds checks, no im2col row goes to memory.  The tile (128 pixels x 32
+ *   channels for Cout <= 32, else 64 x 64) is chosen by Cout alone and the k order is fixed, so an image's output is the same bits in any
+ *   batch and at any position in it.  16-byte loads are used when Cin, ldx, ldw are multiples of 4 and x, w are 16-byte aligned; the bits
+ *   do not depend on that.  A 1 x 1 convolution with H = W = 1 is a plain x w^T product (the fc head).
+ * fm_pool2d_nhwc_f32: x f32 rows (B H W, ldx) -> out f32 rows, C channels, taps visited ky, kx ascending.  FM_POOL_MAX_3X3_S2: valid 3 x 3
+ *   windows at stride 2, Ho = (H - 3) / 2 + 1.  FM_POOL_MAX_3X3_S1P1: stride 1, padding 1 that never wins.  FM_POOL_AVG_3X3_S1P1: stride 1,
+ *   padding 1, count_include_pad = False: the fp32 sum of the valid taps times the fp32 reciprocal of their count.  FM_POOL_GLOBAL_AVG: out
+ *   (B, ldo) = the fp32 sum over the H W rows of an image in row order, divided by H W.
+ * fm_inception_preprocess: in (B, 3, H, W) uint8, or f32 when is_f32 (byte = trunc(255 v) in fp32, clamped to [0, 255]; NaN gives 0) ->
+ *   bilinear resize to 299 x 299 WITHOUT half-pixel offset (TF1 / torch-fidelity) -> (v - 128) / 128, written as rows (B 299 299, 3).
+ *   idx int32 (4, 299) = y0, y1, x0, x1 and wt f32 (2, 299) = wy, wx are the caller's axis tables (device memory): with s = in / 299 in
+ *   double, src = o s, i0 = floor(src), i1 = min(i0 + 1, in - 1), w = src - i0 rounded to fp32.  top = fmaf(r - l, wx, l) on rows y0 and y1,
+ *   then fmaf(bottom - top, wy, top).  Table indices are clamped to the image in the kernel.  One launch.
+ * fm_feature_moments: feats f32 (n, d), row stride ld:  sum f64 (d) += column sums, outer f64 (d, d) += X^T X, count int64 (1) += n.  Every
+ *   output element belongs to one thread and the rows are added in ascending order; a product of two floats is exact in double, so the
+ *   result is the sequential float64 sum bit for bit.  d <= FM_MOMENTS_MAX_D.  Two launches.
+ * Refused (-1) before anything is launched or written: null or misaligned pointers, sizes outside the ranges above, row strides smaller
+ *   than the row, an unknown mode.  No allocation, no host synchronisation. */
+#define FM_CONV2D_MAX_K 7
+#define FM_CONV2D_MAX_PAD 3
+#define FM_POOL_MAX_3X3_S2 0
+#define FM_POOL_MAX_3X3_S1P1 1
+#define FM_POOL_AVG_3X3_S1P1 2
+#define FM_POOL_GLOBAL_AVG 3
+#define FM_INCEPTION_SIZE 299
+#define FM_MOMENTS_MAX_D 4096
+typedef struct fm_conv2d_args {
+    const void* x;
+    const void* w;
+    const void* bias;
+    void* out;
+    int B, H, W, Cin, Cout, KH, KW, stride, pad_h, pad_w;
+    int ldx, ldw, ldo, relu;
+} fm_conv2d_args;
+int fm_conv2d_nhwc_f32(const fm_conv2d_args* a, void* stream);
+int fm_pool2d_nhwc_f32(const void* x, int ldx, void* out, int ldo, int B, int H, int W, int C, int mode, void* stream);
+int fm_inception_preprocess(const void* in, int is_f32, int B, int H, int W, const void* idx, const void* wt, void* out, void* stream);
+int fm_feature_moments(const void* feats, int ld, int n, int d, void* sum, void* outer, void* count, void* stream);
+
 /* ---- lab(not part of the drop-in surface) ------------------------------------------------------------------------------------------
  * Experiment knobs of the GEMM kernels, used by tools/gemm_lab.cpp, the Python tools and the FOURM_NT3_LAB environment switch only: key 0 / 1
  * staggered workgroup start (groups, step), 2 gemm_nt3 mode override, 3 gemm_nt3 ablation flags (gemm_args.h NTArgs::lab), others reserved.

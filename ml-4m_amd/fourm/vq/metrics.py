@@ -11,7 +11,7 @@ Everything is fp32 in, float64 sums and int64 counts in device tensors; the kern
 host; ``compute`` is where a number is asked for.  The definitions ("tokenizer validation metrics") are the contract: torchmetrics
 is not a dependency, and parity with it is not pinned.  Tensors on the CPU raise RuntimeError (there is no CPU path).
 
-Not here: FID, the Inception score and the AlexNet LPIPS metric (they need pretrained weights), and the trainer scripts themselves; codebook
+Not here: the AlexNet LPIPS metric (it needs pretrained weights) and the trainer scripts themselves (FID and the Inception score: fourm.utils.inception); codebook
 usage is ``fourm.vq.vq_utils.compute_codebook_usage``."""
 from typing import Dict, Optional, Sequence, Tuple
 
