@@ -1201,6 +1201,50 @@ int fm_pool2d_nhwc_f32(const void* x, int ldx, void* out, int ldo, int B, int H,
 int fm_inception_preprocess(const void* in, int is_f32, int B, int H, int W, const void* idx, const void* wt, void* out, void* stream);
 int fm_feature_moments(const void* feats, int ld, int n, int d, void* sum, void* outer, void* count, void* stream);
 
+/* LPIPS validation metric (csrc/lpips_metric.hip): the two kernels the AlexNet LPIPS metric of eval_metrics needs beyond the Inception tower's
+ * (fourm/vq/percept_losses/lpips_alex.py, fourm.vq.metrics.LearnedPerceptualImagePatchSimilarity).  fp32, no floating-point atomics, one
+ * summation order per output element: two calls give the same bits.  ADDED without raising FM_ABI_VERSION (it stays 11).
+ *
+ * fm_conv2d_stem_f32: a convolution for image stems, read straight from NCHW pixels.  img f32 (B, Cin, H, W) contiguous.  Per pixel value v:
+ *   when clamp != 0, v = min(max(v, lo), hi); then s = fmaf(v, mul[c], add[c]) (one rounding; mul, add f32 (Cin), or both NULL: s = v).  Zero
+ *   padding applies to s: a tap outside the image contributes 0, not add[c].  out[b, oy, ox, n] = act(bias[n] + acc), acc = ONE fp32
+ *   accumulation chain from 0 over k = (ky KW + kx) Cin + c ascending of s * w[n, k] (the order of fm_conv2d_nhwc_f32).  w: f32 (Cout, KH KW Cin),
+ *   row stride ldw; bias: f32 (Cout) or NULL; out: f32 NHWC rows (B Ho Wo, ldo), columns outside [0, Cout) never written; Ho = (H + 2 pad -
+ *   KH) / stride + 1, Wo likewise; act = ReLU when relu != 0.  Cin in 1..FM_STEM_MAX_CIN, Cout in 1..FM_STEM_MAX_COUT, KH, KW in
+ *   1..FM_STEM_MAX_K, stride in 1..FM_STEM_MAX_STRIDE, pad in 0..FM_STEM_MAX_PAD (both axes), H + 2 pad >= KH, W + 2 pad >= KW, fewer than
+ *   2^31 output rows.  Implicit GEMM on v_mfma_f32_32x32x2_f32 with the gather (bounds-checked against the image) into LDS: no im2col or
+ *   space-to-depth copy goes to memory.  The tile (128 pixels x 32 channels for Cout <= 32, else 64 x 64) is chosen by Cout alone and the k
+ *   order is fixed: an image's output is the same bits in any batch and at any position in it.  One launch.
+ * fm_lpips_score: a, b f32 rows (B P, C) with row strides lda, ldb; w f32 (C).  Per pixel na = sqrtf(eps + sum_c a_c^2), a^ = a / na, b^
+ *   likewise; score[b] += (sum over the P pixels of sum_c w_c (a^_c - b^_c)^2) / P, all fp32.  score: f32 (B), zeroed by the caller before the
+ *   first layer.  A first launch writes one partial per (sample, chunk of FM_LPIPS_SCORE_CHUNK pixels) to scratch (f32, fm_lpips_score_scratch
+ *   values: that function returns the count, or -1), a second adds a sample's partials in chunk order onto score[b].  C % 4 == 0, C <=
+ *   FM_LPIPS_SCORE_MAX_C, lda, ldb % 4 == 0 and >= C, all pointers 16-byte aligned, P >= 1, eps >= 0, B P < 2^31.  By construction: swapping
+ *   a and b changes no bit; a against itself gives exactly 0; a pixel that is all zero on both sides contributes 0 (never NaN) when eps > 0.
+ * Refused (-1) before anything is launched or written: null or misaligned pointers, sizes outside the ranges above, row strides smaller
+ *   than the row, mul without add.  No allocation, no host synchronisation. */
+#define FM_STEM_MAX_CIN 4
+#define FM_STEM_MAX_COUT 128
+#define FM_STEM_MAX_K 11
+#define FM_STEM_MAX_STRIDE 4
+#define FM_STEM_MAX_PAD 5
+#define FM_LPIPS_SCORE_CHUNK 64
+#define FM_LPIPS_SCORE_MAX_C 512
+typedef struct fm_conv2d_stem_args {
+    const void* img;
+    const void* w;
+    const void* bias;
+    const void* mul;
+    const void* add;
+    void* out;
+    int B, Cin, H, W, Cout, KH, KW, stride, pad;
+    int ldw, ldo, relu, clamp, reserved;
+    float lo, hi;
+} fm_conv2d_stem_args;
+int fm_conv2d_stem_f32(const fm_conv2d_stem_args* a, void* stream);
+int fm_lpips_score_scratch(int B, int P);
+int fm_lpips_score(const void* a, int lda, const void* b, int ldb, const void* w, int B, int P, int C, float eps, void* score, void* scratch, void* stream);
+
 /* ---- lab(not part of the drop-in surface) ------------------------------------------------------------------------------------------
  * Experiment knobs of the GEMM kernels, used by tools/gemm_lab.cpp, the Python tools and the FOURM_NT3_LAB environment switch only: key 0 / 1
  * staggered workgroup start (groups, step), 2 gemm_nt3 mode override, 3 gemm_nt3 ablation flags (gemm_args.h NTArgs::lab), others reserved.

@@ -10,15 +10,16 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "fourm", "_lib", "libfourm_hip.so")
-SOURCES = ["api.cpp", "gemm.hip", "gemm_nt_flat.hip", "gemm_nt3.hip", "gemm_nt4.hip", "gemm_tn4.hip", "gemm_skinny.hip", "layernorm.hip", "attention.hip", "select_embed.hip", "loss.hip", "elementwise.hip", "vq.hip", "convnext.hip", "fp32_verify.hip", "sample.hip", "masking.hip", "unet.hip", "unet_f32.hip", "unet_f32_bwd.hip", "lora.hip", "vit_embed.hip", "attn_decode.hip", "clip.hip", "lpips.hip", "train_objective.hip", "metrics.hip", "resize.hip", "pil_resize.hip", "pil_resize16.hip", "clip_text.hip", "knn.hip", "inception.hip"]
+SOURCES = ["api.cpp", "gemm.hip", "gemm_nt_flat.hip", "gemm_nt3.hip", "gemm_nt4.hip", "gemm_tn4.hip", "gemm_skinny.hip", "layernorm.hip", "attention.hip", "select_embed.hip", "loss.hip", "elementwise.hip", "vq.hip", "convnext.hip", "fp32_verify.hip", "sample.hip", "masking.hip", "unet.hip", "unet_f32.hip", "unet_f32_bwd.hip", "lora.hip", "vit_embed.hip", "attn_decode.hip", "clip.hip", "lpips.hip", "train_objective.hip", "metrics.hip", "resize.hip", "pil_resize.hip", "pil_resize16.hip", "clip_text.hip", "knn.hip", "inception.hip", "lpips_metric.hip"]
 
 
 # sample.hip: the sampler's determinism contract needs separately rounded fp32 multiplies and adds (no fused multiply-add)
 # train_objective.hip: the EMA update, the diffusion training pair and the mask concat are bit-exact against torch's separately rounded kernels
 # metrics.hip: the denormalisation in the loads is torch's separately rounded add and halving; the SSIM moments are rounded product by product
 # pil_resize.hip: the HOST coefficient tables must come out as Pillow's doubles do, every multiply and add rounded separately
+# lpips_metric.hip: every fused multiply-add of the stem's affine and of the distance is written as one; nothing else may be fused
 # pil_resize16.hip: the same tables, and Pillow's 16-bit passes accumulate in double on the DEVICE tap by tap: no fused multiply-add there either
-EXTRA_FLAGS = {"sample.hip": ["-ffp-contract=off"], "train_objective.hip": ["-ffp-contract=off"], "metrics.hip": ["-ffp-contract=off"], "pil_resize.hip": ["-ffp-contract=off"], "pil_resize16.hip": ["-ffp-contract=off"]}
+EXTRA_FLAGS = {"sample.hip": ["-ffp-contract=off"], "train_objective.hip": ["-ffp-contract=off"], "metrics.hip": ["-ffp-contract=off"], "pil_resize.hip": ["-ffp-contract=off"], "pil_resize16.hip": ["-ffp-contract=off"], "lpips_metric.hip": ["-ffp-contract=off"]}
 
 
 def hipcc() -> str:

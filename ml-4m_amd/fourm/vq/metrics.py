@@ -3,6 +3,8 @@ run_training_divae.py:1298 ff.), which upstream takes from torchmetrics, as a li
 
     MeanSquaredError, MeanAbsoluteError, PeakSignalNoiseRatio, MultiScaleStructuralSimilarityIndexMeasure, BinaryJaccardIndex
                              the constructor calls of eval_metrics verbatim; ``update(preds, target)`` / ``compute()`` / ``reset()`` / ``.to(device)``
+    LearnedPerceptualImagePatchSimilarity
+                             the AlexNet LPIPS metric of :1486-1491 on fourm.vq.percept_losses.lpips_alex.LpipsAlex (csrc/lpips_metric.hip)
     ReconstructionMetrics    the per-domain part of eval_metrics (:1469-1480, :1513-1553, :1557-1575): takes the decoder output and the prepared
                              input as they are and converts them inside the kernels' loads
     token_histogram          the ``np.bincount`` of :1622 on the device
@@ -11,8 +13,8 @@ Everything is fp32 in, float64 sums and int64 counts in device tensors; the kern
 host; ``compute`` is where a number is asked for.  The definitions ("tokenizer validation metrics") are the contract: torchmetrics
 is not a dependency, and parity with it is not pinned.  Tensors on the CPU raise RuntimeError (there is no CPU path).
 
-Not here: the AlexNet LPIPS metric (it needs pretrained weights) and the trainer scripts themselves (FID and the Inception score: fourm.utils.inception); codebook
-usage is ``fourm.vq.vq_utils.compute_codebook_usage``."""
+Not here: pretrained weights of any kind (the LPIPS metric takes a loaded ``LpipsAlex``; without one its weights are seeded-random) and the trainer
+scripts themselves (FID and the Inception score: fourm.utils.inception); codebook usage is ``fourm.vq.vq_utils.compute_codebook_usage``."""
 from typing import Dict, Optional, Sequence, Tuple
 
 import torch
@@ -25,7 +27,7 @@ MAX_KERNEL_SIZE = 11          # FM_SSIM_MAX_KERNEL
 RAW, DENORM, SIGMOID_PRED = "raw", "denorm", "sigmoid_pred"
 
 __all__ = ["MeanSquaredError", "MeanAbsoluteError", "PeakSignalNoiseRatio", "MultiScaleStructuralSimilarityIndexMeasure", "BinaryJaccardIndex",
-           "ReconstructionMetrics", "token_histogram", "domain_spec", "gaussian_window", "DENSE_FEAT_MODALITIES"]
+           "LearnedPerceptualImagePatchSimilarity", "ReconstructionMetrics", "token_histogram", "domain_spec", "gaussian_window", "DENSE_FEAT_MODALITIES"]
 
 
 def _transform_id(transform):
@@ -258,6 +260,76 @@ class MultiScaleStructuralSimilarityIndexMeasure(_Metric):
         return self._nan() if self.similarity is None else (self.similarity[0] / self.total[0].double()).float()
 
 
+# ---- LPIPS ----------------------------------------------------------------------------------------------------------------------------------------
+class LearnedPerceptualImagePatchSimilarity(_Metric):
+    """Mean (or sum) over all pairs since ``reset`` of the AlexNet LPIPS distance.  ``update(img1, img2)``: (N, 3, H, W) images, H, W >= 31, in
+    [-1, 1], or in [0, 1] with ``normalize=True`` (mapped by 2 x - 1 inside the stem's loads).  ``net``: a ``LpipsAlex`` (load the
+    checkpoints into it: ``LpipsAlex.from_parts``); None builds one with SEEDED-RANDOM weights - no weights are shipped, and such a number
+    compares two tokenizers under one fixed random network, not with published LPIPS values.  The metric owns the network: it follows the
+    metric to the device of the images.
+
+    State: ``sum_scores`` float64 (1,) and ``total`` int64 (1,) on the device, additive (all-reduce them across ranks before ``compute``).
+    ``update`` never synchronises; the per-sample fp32 scores are added to the float64 sum one by one in row order, so two updates of two
+    pairs leave the same state bits as one update of four.  ``compute`` (the one synchronisation): sum / total for 'mean', the sum for
+    'sum', as fp32; NaN when nothing was seen.
+
+    Unlike torchmetrics the input VALUES are not range-checked (that would synchronise): out-of-range pixels are simply evaluated."""
+    _STATE = (("sum_scores", torch.float64, 1), ("total", torch.int64, 1))
+
+    def __init__(self, net_type='alex', reduction='mean', normalize=False, net=None, **kwargs):
+        name = "LearnedPerceptualImagePatchSimilarity"
+        _accept(name, kwargs, **_COMMON)
+        if net_type in ('vgg', 'squeeze'):
+            raise ValueError(f"{name}: net_type={net_type!r} is not built (supported: 'alex')")
+        if net_type != 'alex':
+            raise ValueError(f"{name}: net_type={net_type!r}: 'alex' expected")
+        if reduction not in ('mean', 'sum'):
+            raise ValueError(f"{name}: reduction={reduction!r}: 'mean' or 'sum' expected")
+        if not isinstance(normalize, bool):
+            raise ValueError(f"{name}: normalize={normalize!r}: a bool expected")
+        from fourm.vq.percept_losses.lpips_alex import LpipsAlex
+        if net is not None and not isinstance(net, LpipsAlex):
+            raise TypeError(f"{name}: net has to be a LpipsAlex, got {type(net).__name__}")
+        self.net_type, self.reduction, self.normalize = net_type, reduction, normalize
+        self.net = LpipsAlex() if net is None else net
+        super().__init__()
+
+    def to(self, device):
+        super().to(device)
+        if device is not None:
+            self.net.to(device)
+        return self
+
+    def update(self, img1: torch.Tensor, img2: torch.Tensor) -> None:
+        self._update(img1, img2, self.normalize, False)
+
+    def _update(self, img1, img2, normalize, clamp0):
+        from fourm.utils.inception import ops as iops
+        name = type(self).__name__
+        for t in (img1, img2):
+            if not torch.is_tensor(t) or t.dim() != 4 or t.shape[1] != 3 or t.shape[0] < 1:
+                raise ValueError(f"{name}: images of shape (N, 3, H, W) expected, got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+        if img1.shape != img2.shape:
+            raise ValueError(f"{name}: img1 {tuple(img1.shape)} and img2 {tuple(img2.shape)} differ in shape")
+        _on_gpu(name, img1, img2)
+        device = img1.device
+        self._state_on(device)
+        if next(self.net.parameters()).device != device:
+            self.net.to(device)
+        scores = self.net.scores(img1, img2, normalize, clamp0=clamp0)
+        with torch.no_grad(), torch.cuda.device(device):
+            # the float64 column sum of fm_feature_moments: rows ascending, one thread, continuing from the stored sum; the count rides along
+            iops.feature_moments(scores.view(-1, 1), self.sum_scores, torch.zeros(1, 1, dtype=torch.float64, device=device), self.total)
+
+    def compute(self) -> torch.Tensor:
+        if self.sum_scores is None:
+            return self._nan()
+        s, n = self.sum_scores[0], self.total[0]
+        if self.reduction == 'mean':
+            return (s / n.double()).float()
+        return torch.where(n > 0, s, torch.full_like(s, float("nan"))).float()
+
+
 # ---- the per-domain part of eval_metrics ----------------------------------------------------------------------------------------------------------
 def domain_spec(domain: str) -> Tuple[Optional[int], str, bool, bool]:
     """-> (channels compared (None: all), transform, MS-SSIM?, IoU?) of a domain, upstream's table (run_training_vqvae.py:1469-1480, :1513-1537)."""
@@ -281,9 +353,15 @@ class ReconstructionMetrics:
     """MSE, MAE, PSNR and MS-SSIM or IoU of one domain, as eval_metrics reports them.  ``update(output, images)`` takes the decoder output and the
     prepared input as they are (extra channels such as a validity mask included): the channel slice, the denormalisation (v + 1) / 2, the
     sigmoid of a ``sam_mask`` prediction and the clamp in front of the IoU happen in the kernels' loads, with no intermediate tensor.  One pass
-    gives the three error metrics (and the IoU counts); MS-SSIM takes its pass per scale."""
+    gives the three error metrics (and the IoU counts); MS-SSIM takes its pass per scale.
 
-    def __init__(self, domain: str, data_range: float = 1.):
+    ``lpips``: a ``LearnedPerceptualImagePatchSimilarity`` for domain ``rgb`` or ``normal`` (upstream's :1549): every ``update`` then also feeds
+    it the first three channels of ``output``, clamped to [-1, 1] inside the stem's loads, and of ``images`` - upstream's
+    ``lpips_metric.update(reconst.clamp(0, 1), gt)`` with ``normalize=True`` expressed on the raw [-1, 1] tensors, without the denormalise /
+    renormalise round trip (the instance's own ``normalize`` setting is not consulted) - and ``compute`` reports ``LPIPS`` after ``MS-SSIM``.
+    With the default None the keys and values are unchanged."""
+
+    def __init__(self, domain: str, data_range: float = 1., lpips=None):
         self.domain = domain
         self.channels, self.transform, has_ms_ssim, self.has_iou = domain_spec(domain)
         if isinstance(data_range, bool) or not isinstance(data_range, (int, float)) or not data_range > 0:
@@ -292,6 +370,12 @@ class ReconstructionMetrics:
         self.threshold = 0.5
         self.ms_ssim = MultiScaleStructuralSimilarityIndexMeasure(data_range=self.data_range, reduction='elementwise_mean', normalize=False) if has_ms_ssim else None
         self.sums = self.counts = None
+        if lpips is not None:
+            if not isinstance(lpips, LearnedPerceptualImagePatchSimilarity):
+                raise TypeError(f"ReconstructionMetrics: lpips has to be a LearnedPerceptualImagePatchSimilarity, got {type(lpips).__name__}")
+            if domain not in ('rgb', 'normal'):
+                raise ValueError(f"ReconstructionMetrics: lpips is reported for the domains 'rgb' and 'normal' only, not for {domain!r}")
+        self.lpips = lpips
 
     def reset(self):
         if self.sums is not None:
@@ -299,12 +383,16 @@ class ReconstructionMetrics:
             self.counts.zero_()
         if self.ms_ssim is not None:
             self.ms_ssim.reset()
+        if self.lpips is not None:
+            self.lpips.reset()
 
     def to(self, device):
         if self.sums is not None:
             self.sums, self.counts = self.sums.to(device), self.counts.to(device)
         if self.ms_ssim is not None:
             self.ms_ssim.to(device)
+        if self.lpips is not None:
+            self.lpips.to(device)
         return self
 
     def update(self, output: torch.Tensor, images: torch.Tensor) -> None:
@@ -323,6 +411,8 @@ class ReconstructionMetrics:
         _accumulate_sums(what, output, images, self.sums, self.counts, c_use=c_use, transform=self.transform, iou=self.has_iou, threshold=self.threshold)
         if self.ms_ssim is not None:
             self.ms_ssim._update(output, images, c_use, self.transform)
+        if self.lpips is not None:
+            self.lpips._update(output[:, :3], images[:, :3], False, True)
 
     def compute(self, prefix: str = '[Eval]', eval_size=None) -> Dict[str, float]:
         """upstream's result keys, f'{prefix} MSE@{eval_size}' and so on, with Python floats (the one host synchronisation)."""
@@ -337,6 +427,8 @@ class ReconstructionMetrics:
         results = {key('MSE'): mse, key('MAE'): mae, key('PSNR'): psnr}
         if self.ms_ssim is not None:
             results[key('MS-SSIM')] = self.ms_ssim.compute().item()
+        if self.lpips is not None:
+            results[key('LPIPS')] = self.lpips.compute().item()
         if self.has_iou:
             results[key('IoU')] = nan if self.counts is None else _iou(self.counts).item()
         return results

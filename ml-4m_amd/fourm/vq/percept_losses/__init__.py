@@ -6,6 +6,7 @@ from fourm import _upstream as _up
 
 _up.extend_path(__name__, __path__)          # first: fourm.vq.percept_losses.lpips falls through to upstream's file
 from .clip_loss import OPENAI_CLIP_MEAN, OPENAI_CLIP_STD, ClipPerceptualLoss
+from .lpips_alex import LpipsAlex          # the AlexNet tower of the LPIPS validation METRIC (fourm.vq.metrics), forward only
 from .lpips_loss import LpipsPerceptualLoss
 
-__all__ = ["ClipPerceptualLoss", "OPENAI_CLIP_MEAN", "OPENAI_CLIP_STD", "LpipsPerceptualLoss"]
+__all__ = ["ClipPerceptualLoss", "OPENAI_CLIP_MEAN", "OPENAI_CLIP_STD", "LpipsAlex", "LpipsPerceptualLoss"]
