@@ -1245,6 +1245,29 @@ int fm_conv2d_stem_f32(const fm_conv2d_stem_args* a, void* stream);
 int fm_lpips_score_scratch(int B, int P);
 int fm_lpips_score(const void* a, int lda, const void* b, int ldb, const void* w, int B, int P, int C, float eps, void* score, void* scratch, void* stream);
 
+/* ---- LayerScale on the residual stream and the DINOv2 front end (csrc/layerscale.hip, csrc/dinov2.hip) ------------------------------
+ * DINOv2's block is x = x + gamma1 * proj(attn(norm1(x))); x = x + gamma2 * mlp(norm2(x)) with learned per-channel gammas.  The arithmetic
+ * of both sums is eager torch's: the product gamma[c] * float(delta) is rounded to fp32, then the sum is rounded to fp32 - never one fused
+ * multiply-add - so x_out is the CPU's x + gamma * delta.float() bit for bit.
+ * fm_layernorm_fwd_res_ls: fm_layernorm_fwd_res with gamma f32 (D) in front of the add: x_out = x + gamma[c] * float(delta) (delta bf16),
+ *   y = LN(x_out) in one pass.  y, mean and rstd carry the bits fm_layernorm_fwd gives on that x_out; with gamma == 1 every output has the
+ *   bits of fm_layernorm_fwd_res.  x_out may not alias x.  D % 4 == 0, D <= 2048, leading dims % 4 == 0 and >= D, delta and a bf16 y 8-byte
+ *   aligned, every other pointer 16-byte aligned.
+ * fm_layerscale_add: the same sum without the norm, delta bf16 or f32 (delta_is_f32; fp32 mode: the branch GEMM wrote it with FM_EPI_F32).
+ *   x_out may be x itself (then ldx == ldxo).  D % 4 == 0 (no upper limit), leading dims and alignment as above.
+ * fm_cls_pos_embed: the token assembly of DinoVisionTransformer.  patches bf16 or f32 (B G, ldp): patch-projection rows with the conv bias
+ *   already added; cls f32 (D); reg f32 (n_reg, D) or NULL with n_reg == 0; pos f32 (1 + G, D): the position table of this patch grid.
+ *   out f32 (B T, ldo), T = 1 + n_reg + G: row 0 of a sample = cls + pos[0], rows 1 .. n_reg = reg (no position), row 1 + n_reg + g =
+ *   patch g + pos[1 + g].  One fp32 add per element, row-local.  D % 4 == 0, ldp, ldo % 4 == 0 and >= D, B T < 2^31.
+ * Refused (-1) before anything is launched: null or misaligned pointers, sizes outside the ranges above.  One launch each, no allocation. */
+int fm_layernorm_fwd_res_ls(const void* x, int ldx, const void* delta, int ldd, const void* gamma, void* x_out, int ldxo, const void* w,
+                            const void* b, void* y, int ldy, int y_is_f32, void* mean, void* rstd, const int32_t* row_map, int R, int D,
+                            float eps, void* stream);
+int fm_layerscale_add(const void* x, int ldx, const void* delta, int ldd, int delta_is_f32, const void* gamma, void* x_out, int ldxo,
+                      int R, int D, void* stream);
+int fm_cls_pos_embed(const void* patches, int ldp, int patches_f32, const void* cls, const void* reg, int n_reg, const void* pos,
+                     void* out, int ldo, int B, int G, int D, void* stream);
+
 /* ---- lab(not part of the drop-in surface) ------------------------------------------------------------------------------------------
  * Experiment knobs of the GEMM kernels, used by tools/gemm_lab.cpp, the Python tools and the FOURM_NT3_LAB environment switch only: key 0 / 1
  * staggered workgroup start (groups, step), 2 gemm_nt3 mode override, 3 gemm_nt3 ablation flags (gemm_args.h NTArgs::lab), others reserved.

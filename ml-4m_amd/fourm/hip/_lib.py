@@ -364,7 +364,11 @@ LPIPS_SCORE_CHUNK, LPIPS_SCORE_MAX_C = 64, 512      # FM_LPIPS_SCORE_CHUNK, FM_L
 conv2d_stem_f32 = _sig("fm_conv2d_stem_f32", P(Conv2dStemArgs), vp)
 lpips_score_scratch = _sig("fm_lpips_score_scratch", i32, i32)
 lpips_score = _sig("fm_lpips_score", vp, i32, vp, i32, vp, i32, i32, i32, f32, vp, vp, vp)
-EXPORTS = ["fm_conv2d_stem_f32", "fm_lpips_score_scratch", "fm_lpips_score", "fm_conv2d_nhwc_f32", "fm_pool2d_nhwc_f32", "fm_inception_preprocess", "fm_feature_moments", "fm_row_sqnorms", "fm_knn_query_tile", "fm_knn_splits", "fm_knn_scratch_bytes", "fm_knn_search", "fm_knn_refine_l2", "fm_clip_text_embed", "fm_clip_pair_score_scratch", "fm_clip_pair_score", "fm_l2_normalize_rows", "fm_pil_axis_table_f64", "fm_pil_crop_resize16", "fm_depth_standardize", "fm_pil_axis_table", "fm_pil_crop_resize", "fm_resize_axis_table", "fm_resize_bilinear_fwd", "fm_resize_bilinear_bwd", "fm_resize_nearest","fm_metric_sums_scratch", "fm_metric_sums", "fm_ssim_scale_scratch", "fm_ssim_scale", "fm_avgpool2x2_pair", "fm_token_histogram",
+# LayerScale on the residual stream and the DINOv2 front end (csrc/layerscale.hip, csrc/dinov2.hip)
+layernorm_fwd_res_ls = _sig("fm_layernorm_fwd_res_ls", vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, f32, vp)
+layerscale_add = _sig("fm_layerscale_add", vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, vp)
+cls_pos_embed = _sig("fm_cls_pos_embed", vp, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, vp)
+EXPORTS = ["fm_layernorm_fwd_res_ls", "fm_layerscale_add", "fm_cls_pos_embed", "fm_conv2d_stem_f32", "fm_lpips_score_scratch", "fm_lpips_score", "fm_conv2d_nhwc_f32", "fm_pool2d_nhwc_f32", "fm_inception_preprocess", "fm_feature_moments", "fm_row_sqnorms", "fm_knn_query_tile", "fm_knn_splits", "fm_knn_scratch_bytes", "fm_knn_search", "fm_knn_refine_l2", "fm_clip_text_embed", "fm_clip_pair_score_scratch", "fm_clip_pair_score", "fm_l2_normalize_rows", "fm_pil_axis_table_f64", "fm_pil_crop_resize16", "fm_depth_standardize", "fm_pil_axis_table", "fm_pil_crop_resize", "fm_resize_axis_table", "fm_resize_bilinear_fwd", "fm_resize_bilinear_bwd", "fm_resize_nearest","fm_metric_sums_scratch", "fm_metric_sums", "fm_ssim_scale_scratch", "fm_ssim_scale", "fm_avgpool2x2_pair", "fm_token_histogram",
            "fm_reconst_loss_scratch", "fm_reconst_loss", "fm_scale_f32", "fm_mask_out_samples", "fm_ema_update", "fm_diffusion_pair", "fm_token_usage", "fm_lpips_stem", "fm_lpips_stem_bwd", "fm_maxpool2x2_nhwc", "fm_lpips_distance", "fm_lpips_tap_bwd", "fm_feat_distance", "fm_quick_gelu_bwd", "fm_quick_gelu_bwd_f32", "fm_clip_embed_ln_bwd", "fm_tap_add", "fm_clip_embed_ln", "fm_attn_decode", "fm_vit_patch_rows", "fm_vit_emb_rows", "fm_vit_colsum", "fm_lora_apply", "fm_lora_grad", "fm_vq_assign_wide", "fm_memcodes_assign", "fm_convnext_block", "fm_split3_bf16", "fm_unet_im2col", "fm_groupnorm_nhwc", "fm_add_bf16", "fm_silu_f32_to_bf16", "fm_timestep_embedding", "fm_unet_attention", "fm_diffusion_x0", "fm_quantile_abs",
            "fm_diffusion_step", "fm_unpack_image_u8", "fm_unpack_ids_u16", "fm_unpack_mask_bits", "fm_decoder_attention_from_target", "fm_guidance_combine", "fm_image_mask", "fm_token_budgets", "fm_span_mask", "fm_vq_code_stats", "fm_vq_ema_update", "fm_vq_code_bias", "fm_vq_assign_bias", "fm_vq_code_stats_raw", "fm_vq_ema_update_euclid", "fm_vq_unpatchify", "fm_vq_latent_grad", "fm_tanh_bwd_f32", "fm_embed_rows_f32", "fm_vq_patchify_ex", "fm_vq_cls_emb_bwd", "fm_vq_latent_grad_normalized", "fm_abi_version", "fm_last_error", "fm_gemm_nt", "fm_set_gemm_nt_config", "fm_get_gemm_nt_config", "fm_set_reserved_cus", "fm_get_reserved_cus", "fm_bf16_to_f32_scaled", "fm_add_bf16_f32", "fm_scale_rows_bf16", "fm_gemm_tn", "fm_gemm_tn_multi", "fm_set_gemm_tn_config", "fm_get_gemm_tn_config", "fm_set_tn_transpose_read",
            "fm_get_tn_transpose_read", "fm_layernorm_fwd", "fm_layernorm_fwd_res", "fm_layernorm_bwd", "fm_layernorm_bwd_h", "fm_headnorm_fwd", "fm_headnorm_bwd", "fm_attn_fwd", "fm_attn_bwd",

@@ -38,6 +38,9 @@ HEADS_DENSE_MAX = int(os.environ.get("FOURM_HEADS_DENSE_MAX", "8"))
 # GEMM epilogue: the GEMM becomes a plain bf16 launch (the lock-step kernel), the fp32 read-modify-write of the stream moves from an
 # epilogue all workgroups enter together (~2.8 TB/s) into a streaming kernel (5.5 TB/s).  Bit-identical.  FOURM_DEFER_RESIDUAL=0: fused.
 DEFER_RESIDUAL = os.environ.get("FOURM_DEFER_RESIDUAL", "1") == "1"
+# LayerScale blocks (DINOv2): the scaled residual sum runs in the LayerNorm that follows (fm_layernorm_fwd_res_ls).  FOURM_LS_FUSE=0: every
+# sum is written by fm_layerscale_add and the norm reads it back (the measurement's baseline, tools/time_dinov2.py).  Same bits either way.
+LS_FUSE = os.environ.get("FOURM_LS_FUSE", "1") == "1"
 # Every decoder block normalises the SAME context (fm_utils.py:364, fm.py:514-515): x_hat = (context - mean) * rstd does not depend on the
 # layer.  With bias-free context norms the engine computes x_hat once, keeps gamma_l inside the bf16 image of cross_attn.kv.weight
 # (kv_l = x_hat (W_l diag(gamma_l))^T), sums the layers' gradients with respect to x_hat in ONE long-K GEMM and runs the LayerNorm backward
@@ -175,6 +178,7 @@ def fill_mod_desc(md, d, emb, is_dec: bool, mod_id: int, head_index: int = 0, ra
 class FourMEngine:
     _pending = None            # (engines built without this __init__ - the tokenizer's - start with no deferred residual)
     _drop_now = None           # (per-sample DropPath scale, rows per sample) of the residual branch being computed
+    _ls_now = None             # LayerScale gamma (f32 (D)) of the residual branch being computed: blocks with ls1 / ls2 (DINOv2) only
     drop_uniforms = None       # tests: an iterator of (B,) uniform tensors replacing torch.rand in DropPath
 
     def __init__(self, model):
@@ -579,6 +583,9 @@ class FourMEngine:
         pend = self._pending
         if pend is not None and pend[0] is x:      # x = residual + delta is still owed: this norm computes and stores it on the way
             self._pending = None
+            if len(pend) > 4:                      # LayerScale: x = residual + gamma * delta (fm_layernorm_fwd_res_ls)
+                ops.layernorm_fwd(pend[1], norm.weight, norm.bias, y, mean, rstd, row_map=row_map, eps=norm.eps, R=R, delta=pend[2], x_out=x, gamma=pend[4])
+                return y
             ops.layernorm_fwd(pend[1], norm.weight, norm.bias, y, mean, rstd, row_map=row_map, eps=norm.eps, R=R, delta=pend[2], x_out=x)
             return y
         self._settle()
@@ -612,6 +619,8 @@ class FourMEngine:
         """x_out = x_res + a W^T (+ bias): fused in the GEMM epilogue, or (defer) a bf16 GEMM whose sum is owed to the next _ln(x_out).
         With stochastic depth active (self._drop_now = (per-sample scale, rows per sample)) the branch output is scaled first."""
         drop = self._drop_now
+        if self._ls_now is not None:
+            return self._residual_ls(a, lin, x_res, x_out, R, N, K, defer, self._ls_now)
         if drop is not None and self.fp32:
             raise NotImplementedError("drop_path in the fp32 verification mode")
         if drop is not None or (defer and DEFER_RESIDUAL and not self.fp32):
@@ -627,6 +636,22 @@ class FourMEngine:
         else:
             ops.gemm_nt(a, self.w(lin.weight), x_out, epilogue=L.EPI_RESIDUAL, res=x_res, bias=lin.bias, M=R, N=N, K=K)
             self._lora_fwd(lin, a, x_out, R, sv, tag, key)
+
+    def _residual_ls(self, a, lin, x_res, x_out, R, N, K, defer, gamma):
+        """x_out = x_res + gamma * (a W^T + bias), LayerScale (inference towers: no DropPath, no adapters, nothing saved).  The branch GEMM
+        writes delta in the activation type - bf16 as under autocast, or fp32 with FM_EPI_F32 in the fp32 mode - and the scaled sum, product and
+        sum rounded separately as eager torch rounds them, is owed to the next _ln(x_out) (bf16 delta, defer) or written by fm_layerscale_add."""
+        if self._drop_now is not None or is_lora(lin):
+            raise NotImplementedError("LayerScale blocks run without DropPath and LoRA adapters (inference towers)")
+        self._settle()
+        delta = self.ws.get("fwd.delta", (x_out.shape[0], N), self.adt)
+        if self.fp32:
+            ops.gemm_nt(a, self.w(lin.weight), delta, epilogue=L.EPI_F32, bias=lin.bias, M=R, N=N, K=K)
+        else:
+            ops.gemm_nt(a, self.w(lin.weight), delta, bias=lin.bias, M=R, N=N, K=K)
+        self._pending = (x_out, x_res, delta, R, gamma)
+        if self.fp32 or not (defer and LS_FUSE):
+            self._settle()
 
     def _drop_scales(self, blk, B, n, sv, dp):
         """Per-branch DropPath scales of one block: ``dp`` when given (checkpoint recompute), freshly drawn in training mode, else None."""
@@ -650,7 +675,9 @@ class FourMEngine:
     def _settle(self):
         """A deferred residual sum nobody normalised (a caller outside the trunk loops wants the stream itself): write it now."""
         pend, self._pending = self._pending, None
-        if pend is not None:
+        if pend is not None and len(pend) > 4:      # LayerScale: x_out = x_res + gamma * delta
+            ops.layerscale_add(pend[1], pend[2], pend[4], pend[0], pend[3])
+        elif pend is not None:
             x_out, x_res, delta, R = pend
             ops.add_bf16_to_f32(x_res, delta, x_out, R)
 
@@ -741,12 +768,15 @@ class FourMEngine:
         h1 = self._ln(blk.norm1, x_in, self._buf(sv, tag, "h1", (Rp, D), bf), R, sv, "n1", tag)
         x_mid = self._buf(sv, tag, "x_mid", (Rp, D), f32)
         self._drop_now = (dp[0], N) if dp else None
+        self._ls_now = getattr(blk, "ls1", None)
         self._self_attn_fwd(blk.attn, h1, x_in, x_mid, B, N, R, Rp, mask, sv, tag)
+        self._ls_now = None
         h2 = self._ln(blk.norm2, x_mid, self._buf(sv, tag, "h2", (Rp, D), bf), R, sv, "n2", tag)
         x_out = self.ws.get(out_name or (tag + ".x_out" if sv is not None else "scratch.x_out" + tag[-1:]), (Rp, D), f32)
         self._drop_now = (dp[1], N) if dp else None
+        self._ls_now = getattr(blk, "ls2", None)
         self._mlp_fwd(blk.mlp, h2, x_mid, x_out, R, Rp, sv, tag, defer=defer_out)
-        self._drop_now = None
+        self._drop_now = self._ls_now = None
         if sv is not None:
             sv["x_in"] = x_in
         return x_out

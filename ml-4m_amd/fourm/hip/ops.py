@@ -289,9 +289,16 @@ def make_groups(entries, device):
 # ---------------------------------------------------------------------------------------------
 # LayerNorm
 # ---------------------------------------------------------------------------------------------
-def layernorm_fwd(x, w, b, y, mean=None, rstd=None, row_map=None, eps=1e-6, R=None, delta=None, x_out=None):
-    """y = LN(x) - or, with ``delta`` (bf16) and ``x_out`` (f32): x_out = x + delta, y = LN(x_out) in one pass."""
+def layernorm_fwd(x, w, b, y, mean=None, rstd=None, row_map=None, eps=1e-6, R=None, delta=None, x_out=None, gamma=None):
+    """y = LN(x) - or, with ``delta`` (bf16) and ``x_out`` (f32): x_out = x + delta, y = LN(x_out) in one pass.  ``gamma`` (f32 (D), with
+    delta): LayerScale, x_out = x + gamma * delta with the product and the sum rounded separately (fm_layernorm_fwd_res_ls)."""
     R = x.shape[0] if R is None else R
+    if gamma is not None:
+        assert delta is not None and delta.dtype == torch.bfloat16 and gamma.dtype == torch.float32 and gamma.numel() == w.numel()
+        with _prof("layernorm_fwd", 0.0, R * w.numel() * (10 + y.element_size())):
+            L.check(L.layernorm_fwd_res_ls(_p(x), _ld(x), _p(delta), _ld(delta), _p(gamma), _p(x_out), _ld(x_out), _p(w), _p(b), _p(y), _ld(y),
+                                           1 if y.dtype == torch.float32 else 0, _p(mean), _p(rstd), _p(row_map), R, w.numel(), eps, _stream()))
+        return y
     if delta is not None:
         with _prof("layernorm_fwd", 0.0, R * w.numel() * (10 + y.element_size())):
             L.check(L.layernorm_fwd_res(_p(x), _ld(x), _p(delta), _ld(delta), _p(x_out), _ld(x_out), _p(w), _p(b), _p(y), _ld(y),
@@ -628,6 +635,27 @@ def add_bf16_to_f32(x, delta, out, R=None):
     R = x.shape[0] if R is None else R
     assert x.is_contiguous() and delta.is_contiguous() and out.is_contiguous() and x.shape[1] == delta.shape[1] == out.shape[1]
     L.check(L.add_bf16_f32(_p(x), _p(delta), _p(out), R * x.shape[1], _stream()))
+    return out
+
+
+@_timed("casts")
+def layerscale_add(x, delta, gamma, out, R=None, D=None):
+    """out[:R, :D] = x + gamma * float(delta) (delta bf16 or f32; product and sum rounded separately; out may be x): fm_layerscale_add."""
+    R = x.shape[0] if R is None else R
+    D = gamma.numel() if D is None else D
+    assert delta.dtype in (torch.bfloat16, torch.float32) and x.dtype == out.dtype == gamma.dtype == torch.float32 and gamma.numel() == D
+    L.check(L.layerscale_add(_p(x), _ld(x), _p(delta), _ld(delta), 1 if delta.dtype == torch.float32 else 0, _p(gamma), _p(out), _ld(out), R, D, _stream()))
+    return out
+
+
+def cls_pos_embed(patches, cls, reg, pos, out, B, G, D):
+    """DINOv2's token assembly (fm_cls_pos_embed): out (B * (1 + n_reg + G), D) f32 from patch rows (bf16 / f32), the class token, the register
+    rows (or None) and the position table (1 + G, D) of this grid."""
+    n_reg = 0 if reg is None else reg.shape[-2]
+    assert cls.dtype == pos.dtype == out.dtype == torch.float32 and pos.is_contiguous() and pos.numel() == (1 + G) * D and cls.numel() == D
+    assert reg is None or (reg.dtype == torch.float32 and reg.is_contiguous() and reg.shape[-1] == D)
+    L.check(L.cls_pos_embed(_p(patches), _ld(patches), 1 if patches.dtype == torch.float32 else 0, _p(cls), _p(reg), n_reg, _p(pos), _p(out), _ld(out),
+                            B, G, D, _stream()))
     return out
 
 

@@ -12,8 +12,11 @@ only decodes (``Image.open`` + ``convert``), and all crops of a loader batch are
 
 Tasks: ``rgb`` (RGB, upstream's tokenizer statistics mean = std = 0.5, IMAGENET_INCEPTION_*), ``normal`` (RGB, mean = std = 0.5, channel 0
 becomes 255 - v in flipped crops), ``semseg*`` (``convert('P')``, always nearest, int64 class maps; ``semseg_coco`` is shifted up by one
-as upstream's registry does).  Refused by name: depth, --mask_value, SAM instances, the feature tasks (CLIP / DINOv2 / ImageBind) and
---corrupt_samples_log; see REFUSED.  ``--tokenizer_ckpt`` names a checkpoint file directly (``--tokenizer_id`` is resolved under
+as upstream's registry does), and the feature tasks ``CLIP-B16``, ``DINOv2-B14``, ``DINOv2-B14-global``: the images are read from the ``rgb``
+folder with rgb's crops and normalisation, the frozen tower (fourm/utils/clip, fourm/utils/dinov2) turns every crop into a feature map or a
+global embedding, and the tokenizer reads that (fourm.data.features).  The tower's weights come from a local state-dict file named by the
+environment variable FOURM_FEATURE_EXTRACTOR_CKPT (there is no flag for it: the command line stays upstream's); unset, the task is refused.
+Refused by name: depth, --mask_value, SAM instances, ImageBind and any other feature task, and --corrupt_samples_log; see REFUSED.  ``--tokenizer_ckpt`` names a checkpoint file directly (``--tokenizer_id`` is resolved under
 ``--tokenizers_root`` as upstream does)."""
 import argparse
 import datetime
@@ -35,13 +38,12 @@ TASKS = {      # task -> (Pillow mode, mean, std, channels inverted on flip, out
     "rgb": ("RGB", (0.5, 0.5, 0.5), (0.5, 0.5, 0.5), (), "float32"),
     "normal": ("RGB", (0.5, 0.5, 0.5), (0.5, 0.5, 0.5), (0,), "float32"),
 }
+FEATURE_TASKS = ("CLIP-B16", "DINOv2-B14", "DINOv2-B14-global")      # fourm.data.features.FEATURE_TASKS: the frozen tower runs in front of the tokenizer
 REFUSED = {
     "depth": "16-bit depth maps do not go through Pillow's 8-bit resize path (and are standardised per crop)",
     "sam_instance": "SAM instances are sets of masks with boxes, not one image per file",
     "sam_mask": "SAM instances are sets of masks with boxes, not one image per file",
-    "CLIP-B16": "feature tasks need the frozen feature extractor in front of the tokenizer",
-    "DINOv2-B14": "feature tasks need the frozen feature extractor in front of the tokenizer",
-    "DINOv2-B14-global": "feature tasks need the frozen feature extractor in front of the tokenizer",
+    "feature": "the feature tasks whose frozen feature extractor is built here are CLIP-B16, DINOv2-B14 and DINOv2-B14-global",
     "ImageBind-H14": "feature tasks need the frozen feature extractor in front of the tokenizer",
     "ImageBind-H14-global": "feature tasks need the frozen feature extractor in front of the tokenizer",
 }
@@ -58,7 +60,7 @@ VALUE_FLAGS = [
     ("--n_crops", int, 1, "crops per image: the first is the unflipped centre crop, any further ones are random crops with a random flip"),
     ("--min_crop_scale", float, 0.8, "smallest area fraction of a random crop"),
     ("--input_size", int, 224, "side of the square every crop is resized to"),
-    ("--task", str, "rgb", "modality to tokenize: rgb, normal or semseg*"),
+    ("--task", str, "rgb", "modality to tokenize: rgb, normal, semseg*, CLIP-B16, DINOv2-B14 or DINOv2-B14-global"),
     ("--mask_value", float, None, "refused by this script (masking with the valid-mask modality is not built)"),
     ("--resample_mode", str, None, "Pillow filter of the resize: bilinear, bicubic, nearest; unset means Pillow's default (bicubic)"),
     ("--corrupt_samples_log", str, None, "refused by this script (delete the bad token files and run again)"),
@@ -104,13 +106,19 @@ def task_config(args):
         raise NotImplementedError("--mask_value is not supported here: the valid-mask modality and its masking are not part of this script")
     if args.corrupt_samples_log is not None:
         raise NotImplementedError("--corrupt_samples_log is not supported here: delete the corrupt token files and run again")
-    for key, name in ((task, task), ("depth", "depth"), ("sam", "sam_instance"), ("CLIP", "CLIP-B16"), ("DINO", "DINOv2-B14"), ("ImageBind", "ImageBind-H14")):
-        if key in task and name in REFUSED:
+    for key, name in ((task, task), ("depth", "depth"), ("sam", "sam_instance"), ("CLIP", "feature"), ("DINO", "feature"), ("ImageBind", "ImageBind-H14")):
+        if key in task and name in REFUSED and task not in FEATURE_TASKS:
             raise NotImplementedError(f"task {task!r} is not supported here: {REFUSED[name]}")
     if args.resample_mode not in (None, "bilinear", "bicubic", "nearest"):
         raise ValueError(f"--resample_mode {args.resample_mode}: one of bilinear, bicubic, nearest (or leave it unset)")
     if args.n_crops < 1 or args.input_size < 1 or args.batch_size < 1 or args.batch_size_dataloader < 1:
         raise ValueError("--n_crops, --input_size, --batch_size and --batch_size_dataloader are positive")
+    if task in FEATURE_TASKS:
+        # upstream's loader task of a feature task is rgb (save_vq_tokens.py:216): the same crops and (x - 0.5) / 0.5 normalisation go to the
+        # extractor unchanged.  Its weights: a local state-dict file named by FOURM_FEATURE_EXTRACTOR_CKPT (refused here when unset or missing)
+        from fourm.data.features import checkpoint_path
+        checkpoint_path(task)
+        return (*TASKS["rgb"], args.resample_mode, 0)
     if task in TASKS:
         return (*TASKS[task], args.resample_mode, 0)
     if task.startswith("semseg"):
@@ -169,9 +177,11 @@ def settings_for(sample, shape, root, args):
     return np.load(path)
 
 
-def main(args, model=None):
-    """Returns (images tokenized, seconds of the loop).  ``model``: a tokenizer already on the device (else loaded from the arguments)."""
+def main(args, model=None, extractor=None):
+    """Returns (images tokenized, seconds of the loop).  ``model``: a tokenizer already on the device (else loaded from the arguments);
+    ``extractor``: the feature network of a feature task (else built from the file FOURM_FEATURE_EXTRACTOR_CKPT names)."""
     mode, mean, std, invert, out, resample, shift = task_config(args)
+    feature = args.task in FEATURE_TASKS
     import torch
     from fourm.data.crops import crop_resize
     from fourm.vq import tokenize_sub_batches
@@ -187,9 +197,14 @@ def main(args, model=None):
     if model is None:
         model = load_tokenizer(args)
     model = model.to(device).eval()
+    if feature:
+        from fourm.data.features import feature_maps, load_feature_extractor
+        if extractor is None:
+            extractor = load_feature_extractor(args.task)
+        extractor = extractor.to(device).eval().requires_grad_(False)
     root = os.path.join(args.data_root, args.split)
     tokens_root = os.path.join(root, f"{args.task}_{args.folder_suffix}")
-    samples = find_samples(os.path.join(root, args.task))[rank::world]
+    samples = find_samples(os.path.join(root, "rgb" if feature else args.task))[rank::world]
     samples = [s for s in samples if not os.path.exists(os.path.join(tokens_root, s[1], f"{s[2]}.npy"))]
     print(f"{len(samples)} images to tokenize ({args.task}, {args.n_crops} crops each); crop settings are {'only loaded' if args.force_load_crop else 'loaded or drawn'}")
     start, done = time.time(), 0
@@ -207,7 +222,10 @@ def main(args, model=None):
                     raise ValueError(f"crop settings of {s[1]}/{s[2]}: shape {st.shape}, expected {(args.n_crops, 5)}")
             crops = crop_resize(images, settings, args.input_size, resample=resample, mean=mean, std=std, invert_on_flip=invert, out=out)
             with torch.no_grad():
-                toks = tokenize_sub_batches(model, crops.split(args.batch_size, dim=0))
+                subs = crops.split(args.batch_size, dim=0)
+                if feature:          # (the towers run on the current stream; the tokenizer's sub-batches then overlap as for image tasks)
+                    subs = [feature_maps(args.task, extractor, sb) for sb in subs]
+                toks = tokenize_sub_batches(model, subs)
             toks = torch.cat([t.reshape(t.shape[0], -1) for t in toks]).cpu().numpy().astype(np.int16)
             toks = toks.reshape(len(batch), args.n_crops, -1)
             for s, t in zip(batch, toks):
